@@ -8,6 +8,18 @@ one complete suffix-array construction (every doubling round: radix passes,
 re-rank, read-backs) from text resident in HBM to SA resident in HBM.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--n N] [--kind dna]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: it generates the text, runs W
+warm-up and K timed builds and prints the line (its per-round and per-kernel
+fields are the HIP-event stats the timed builds themselves return).
+`--dump-outputs DIR` also writes what the last timed build returned (the
+suffix array) as DIR/*.npy, see dump_outputs().  `--full` adds everything that
+takes runs of its own: the O(n) check of the SA ("verified", and the non-zero
+exit when it fails), "post_build" (LCP + check timings), "reference_schedule",
+"cpu_baseline" and the rocprof "traffic" of the roofline; without it those
+fields are null.  --no-cpu-baseline, --no-reference-schedule and --no-lcp
+drop single legs of a --full run.
 
 N = 1: the single-GPU builder (libsa_hip sa_build_device); "scaling":
 "strong" (the 1-GPU point of the strong-scaling curve).
@@ -81,6 +93,11 @@ def parse():
     ap.add_argument("--n", type=int, default=1 << 30)
     ap.add_argument("--kind", default="dna", choices=sorted(ALPHABETS) + ["degenerate"])
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the last step's suffix array to DIR as .npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the O(n) check, the LCP / check timings, the "
+                         "reference schedule, the CPU baseline and the rocprof traffic look-up")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample-n", type=int, default=1 << 26)
     ap.add_argument("--no-reference-schedule", action="store_true",
@@ -211,6 +228,56 @@ def timed(steps, warmup, fn, barrier):
     return time.perf_counter() - t0, res
 
 
+DUMP_WHOLE_MAX = 1 << 22   # an SA of at most this many entries is written whole (float64: 32 MiB)
+DUMP_SAMPLE = 1 << 21      # a longer one: its entries at this many seeded positions (2 x 16 MiB) ...
+DUMP_BLOCKS = 1 << 20      # ... and the sums of at most this many equal blocks of it (8 MiB)
+DUMP_SEED = 0x5A
+
+
+def dump_outputs(path: str, sa, n: int, torch) -> dict:
+    """--dump-outputs: what the last timed build returned, the suffix array
+    `sa` (device tensor of n entries: u32 positions in int32, or int64), as
+    float64 .npy files under `path` (every position is below 2^53, so exact).
+    n <= DUMP_WHOLE_MAX: sa.npy, the whole array.  Larger: sa_sample_pos.npy
+    (DUMP_SAMPLE positions drawn once from numpy's default_rng(DUMP_SEED),
+    ascending -- a function of n alone), sa_sample.npy (the SA's entries
+    there) and sa_block_sums.npy (the sum of each block of ceil(n /
+    DUMP_BLOCKS) consecutive entries, so every entry of the SA enters the
+    dump).  Same arguments, same text, hence the same files from a correct
+    build.  Returns {file: entries} for the result line."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+
+    def val(x):
+        x = x.to(torch.int64)
+        return x & 0xFFFFFFFF if sa.dtype == torch.int32 else x
+
+    def put(name, t):
+        arr = t.cpu().numpy().astype(np.float64)
+        np.save(os.path.join(path, name), arr)
+        return arr.size
+
+    sa = sa[:n]
+    if n <= DUMP_WHOLE_MAX:
+        return {"sa.npy": put("sa.npy", val(sa))}
+    pos = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_SAMPLE, dtype=np.int64))
+    d_pos = torch.from_numpy(pos).to(sa.device)
+    files = {"sa_sample_pos.npy": put("sa_sample_pos.npy", d_pos), "sa_sample.npy": put("sa_sample.npy", val(sa[d_pos]))}
+    B = -(-n // DUMP_BLOCKS)
+    nb = -(-n // B)
+    sums = torch.zeros(nb, dtype=torch.int64, device=sa.device)
+    per = max(1, (1 << 26) // B)   # blocks per pass: at most 2^26 entries widened to int64 at a time
+    for b0 in range(0, nb, per):
+        b1 = min(nb, b0 + per)
+        x = val(sa[b0 * B: min(n, b1 * B)])
+        pad = (b1 - b0) * B - x.numel()
+        if pad:
+            x = torch.cat([x, x.new_zeros(pad)])
+        sums[b0:b1] = x.view(b1 - b0, B).sum(1)
+    files["sa_block_sums.npy"] = put("sa_block_sums.npy", sums)
+    return files
+
+
 def reference_schedule(b, d_text, n, d_sa, sptr, a, torch, dev, reps: int = 2) -> dict:
     """The north-star-shaped schedule beside the packed headline: one
     doubling round per h = 1, 2, 4, ... (manber_myers.c:97-125), each a
@@ -294,10 +361,12 @@ def run_single(a, torch, dev, world, rank, barrier):
     bkw = dict(stream=sptr, profile=profile, schedule=a.schedule, init_chars=a.init_chars, radix=a.radix,
                round1=a.round1)
     elapsed, stats = timed(a.steps, a.warmup, lambda: b.build(d_text, n, d_sa, **bkw), barrier)
-    verified = b.check(d_text, n, d_sa, stream=sptr)
-    post = post_build(b, d_text, n, d_sa, sptr, torch, dev) if (world == 1 and not a.no_lcp) else None
+    dumped = dump_outputs(a.dump_outputs, d_sa, n, torch) if (a.dump_outputs and rank == 0) else None
+    # everything below that runs the GPU again is --full only
+    verified = b.check(d_text, n, d_sa, stream=sptr) if a.full else None
+    post = post_build(b, d_text, n, d_sa, sptr, torch, dev) if (a.full and world == 1 and not a.no_lcp) else None
     ref_sched = None
-    if world == 1 and a.schedule == "packed" and not a.no_reference_schedule:
+    if a.full and world == 1 and a.schedule == "packed" and not a.no_reference_schedule:
         ref_sched = reference_schedule(b, d_text, n, d_sa, sptr, a, torch, dev)
 
     rounds = stats[-1]["rounds"]
@@ -324,7 +393,7 @@ def run_single(a, torch, dev, world, rank, barrier):
             per_launch = kern[dom]["bytes"] / kern[dom]["launches"]
             ach = per_launch / avg_s / 1e9
             traffic = traffic_src = None
-            pmc = pmc_summary(n, a.kind, SRC_HASH)
+            pmc = pmc_summary(n, a.kind, SRC_HASH) if a.full else None
             if pmc:
                 skind = {"scatter_first": "scatter_first" if bucketed else "scatter_iota"}.get(dom, dom)
                 traffic = pmc.get("traffic_bytes_per_launch", {}).get(skind)
@@ -374,6 +443,7 @@ def run_single(a, torch, dev, world, rank, barrier):
         "round1": stats[-1].get("round1"),
         "largest_window": stats[-1].get("largest_window"),
         "verified": verified,
+        "dumped_outputs": dumped,
         "roofline": roofline,
         "kernels_gbs": per_kernel,
         "kernels_ms_per_step": {k: round(v["ms"] / a.steps, 3) for k, v in kern.items()} if profile else None,
@@ -513,14 +583,17 @@ def run_distributed(a, torch, dev, world, rank, barrier):
         recs = [rec]
     sa_local, sa_off = holder["sa"]
     d_text = ops.textbuf[:n] if world > 1 else d_slice   # the text as the last build gathered it
-    # verification: the full SA gathered to every rank, O(n) check on rank 0
-    verified = None
-    if n <= 0xFFFFFFFF:
+    # --full verification (and --dump-outputs): the full SA gathered to every
+    # rank, O(n) check (the SA dumped) on rank 0
+    verified = dumped = None
+    if n <= 0xFFFFFFFF and (a.full or a.dump_outputs):
         sa = gather_sa(sa_local, sa_off, n)
-        if rank == 0:
+        if rank == 0 and a.dump_outputs:
+            dumped = dump_outputs(a.dump_outputs, sa, n, torch)
+        if rank == 0 and a.full:
             verified = ops.b.check(d_text, n, sa.to(torch.int32))
         del sa
-    if world > 1:
+    if world > 1 and a.full:
         v = torch.tensor([1 if verified in (True, None) else 0], dtype=torch.int64, device=dev)
         dist.broadcast(v, 0)
         verified = bool(v.item()) if n <= 0xFFFFFFFF else None
@@ -541,6 +614,7 @@ def run_distributed(a, torch, dev, world, rank, barrier):
              "host_syncs_driver_per_build": st.get("host_syncs_driver"),
              "host_syncs_native_per_build": st.get("host_syncs_native"),
              "verified": verified,
+             "dumped_outputs": dumped,
              "note": "range-partitioned build from a range-partitioned string: the text all_gather, then each rank "
                      "sorts the suffixes of its bucket range from its text copy; rank requests/answers by RCCL "
                      "all_to_all between doubling rounds; roofline = the slowest rank's dominant round-1 kernel"}
@@ -589,6 +663,7 @@ def main():
         "n_gpus": world,
         "steps": a.steps,
         "warmup": a.warmup,
+        "full": a.full,
         "ms_per_step": round(ms_per_step, 3),
         "higher_is_better": True,
         "scaling": "weak" if (world > 1 and not distributed) else "strong",
@@ -605,7 +680,7 @@ def main():
     }
     out.update(extra)
     out["cpu_baseline"] = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(a.kind, min(a.cpu_sample_n, a.n), a.seed)
     if rank == 0:
         line = json.dumps(out)

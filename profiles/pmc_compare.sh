@@ -11,7 +11,7 @@ S1="SQ_WAVES SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAIT_INST_LDS SQ_LDS_BA
 S2="SQ_WAIT_ANY SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_INSTS_BRANCH SQ_WAIT_INST_ANY"
 for set in 1 2; do
   eval "C=\$S$set"
-  timeout -s KILL 90 rocprofv3 --pmc $C --output-format csv -d "$out/b$set" -o b -- python3 bench.py --no-cpu-baseline --no-profile --steps 1 --warmup 0 > "$out/b$set.log" 2>&1 || exit $?
+  timeout -s KILL 90 rocprofv3 --pmc $C --output-format csv -d "$out/b$set" -o b -- python3 bench.py --full --no-cpu-baseline --no-profile --steps 1 --warmup 0 > "$out/b$set.log" 2>&1 || exit $?
   timeout -s KILL 90 rocprofv3 --pmc $C --output-format csv -d "$out/m$set" -o m -- hpc_suffix_array_amd/csrc/build/microbench_bucket 30 1 28 > "$out/m$set.log" 2>&1 || exit $?
 done
 python3 - "$out" <<'PY'

@@ -7,9 +7,9 @@ out=gpurun_out/pmc_$tag
 mkdir -p "$out"
 export TMPDIR=/tmp
 timeout -s KILL 90 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_BUSY_CYCLES SQ_WAVE_CYCLES \
-    --output-format csv -d "$out/sq" -o sq -- python3 bench.py --no-cpu-baseline --no-profile --steps 1 --warmup 0 "$@" > "$out/sq.log" 2>&1 || exit $?
+    --output-format csv -d "$out/sq" -o sq -- python3 bench.py --full --no-cpu-baseline --no-profile --steps 1 --warmup 0 "$@" > "$out/sq.log" 2>&1 || exit $?
 timeout -s KILL 90 rocprofv3 --pmc SQ_WAIT_ANY SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_INST_CYCLES_VMEM_RD SQ_INSTS_BRANCH \
-    --output-format csv -d "$out/sq2" -o sq2 -- python3 bench.py --no-cpu-baseline --no-profile --steps 1 --warmup 0 "$@" > "$out/sq2.log" 2>&1 || exit $?
+    --output-format csv -d "$out/sq2" -o sq2 -- python3 bench.py --full --no-cpu-baseline --no-profile --steps 1 --warmup 0 "$@" > "$out/sq2.log" 2>&1 || exit $?
 python3 - "$out" <<'PY'
 import csv, glob, sys, collections
 out = sys.argv[1]

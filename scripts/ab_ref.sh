@@ -4,7 +4,7 @@
 # ab/<variant> (scripts/ab_build_variants.sh), interleaved.  A variant named
 # env:NAME=VALUE runs the default library with that environment variable.
 set -e
-mkdir -p gpurun_out/abref
+mkdir -p results/abref
 for v in default "$@" default "$@"; do
   unset SA_LIB_PATH
   envs=()
@@ -13,8 +13,8 @@ for v in default "$@" default "$@"; do
     env:*) envs=("${v#env:}") ;;
     *) export SA_LIB_PATH=$PWD/ab/$v/libsa_hip.so ;;
   esac
-  log=gpurun_out/abref/$(echo "$v" | tr ':=/' '___').log
-  env "${envs[@]}" timeout -k 10 120 python -u bench.py --schedule reference --no-cpu-baseline --steps 3 --warmup 1 > "$log" 2>&1
+  log=results/abref/$(echo "$v" | tr ':=/' '___').log
+  env "${envs[@]}" timeout -k 10 120 python -u bench.py --full --schedule reference --no-cpu-baseline --steps 3 --warmup 1 > "$log" 2>&1
   python - "$v" "$log" <<'PY'
 import json,sys
 d=json.loads([l for l in open(sys.argv[2]) if l.startswith('{')][0])

@@ -1,11 +1,11 @@
 #!/bin/bash
 # GPU box (bash scripts/ab_run.sh <variants>): bench the default library and each ab/<variant>, interleaved
 set -e
-mkdir -p gpurun_out/ab
+mkdir -p results/ab
 for v in default "$@" default "$@"; do
   if [ "$v" = default ]; then unset SA_LIB_PATH; else export SA_LIB_PATH=$PWD/${AB_DIR:-ab}/$v/libsa_hip.so; fi
-  timeout -k 10 120 python -u bench.py --no-cpu-baseline --no-reference-schedule --steps 10 --warmup 2 > gpurun_out/ab/$v.log 2>&1
-  python - "$v" gpurun_out/ab/$v.log <<'PY'
+  timeout -k 10 120 python -u bench.py --full --no-cpu-baseline --no-reference-schedule --steps 10 --warmup 2 > results/ab/$v.log 2>&1
+  python - "$v" results/ab/$v.log <<'PY'
 import json,sys
 d=json.loads([l for l in open(sys.argv[2]) if l.startswith('{')][0])
 k=d['kernels_ms_per_step']

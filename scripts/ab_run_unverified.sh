@@ -2,13 +2,13 @@
 # GPU box: like ab_run.sh, for timing-only variants whose suffix arrays are
 # wrong by construction (bench.py exits non-zero on the failed check; the
 # kernel times are still printed)
-mkdir -p gpurun_out/ab
+mkdir -p results/ab
 for v in default "$@" default "$@"; do
   if [ "$v" = default ]; then unset SA_LIB_PATH; else export SA_LIB_PATH=$PWD/ab/$v/libsa_hip.so; fi
-  timeout -k 10 120 python -u bench.py --no-cpu-baseline --no-reference-schedule --steps 10 --warmup 2 > gpurun_out/ab/$v.log 2>&1
+  timeout -k 10 120 python -u bench.py --full --no-cpu-baseline --no-reference-schedule --steps 10 --warmup 2 > results/ab/$v.log 2>&1
   rc=$?
   if [ $rc -ne 0 ] && [ $rc -ne 3 ]; then echo "$v: rc $rc"; exit $rc; fi
-  python - "$v" gpurun_out/ab/$v.log <<'PY'
+  python - "$v" results/ab/$v.log <<'PY'
 import json,sys
 d=json.loads([l for l in open(sys.argv[2]) if l.startswith('{')][0])
 k=d['kernels_ms_per_step']

@@ -4,7 +4,7 @@
 efficiency columns, a summary table) and of its CUDA sweep
 (benchmark_cuda_kaggle.py:200-289 -- speedup_vs_cpu), over MI355X GPUs.
 
-Each configuration runs bench.py (one process per GPU; N > 1 through
+Each configuration runs bench.py --full (one process per GPU; N > 1 through
 torch.distributed.run on 127.0.0.1, RCCL) on the seeded synthetic text of
 SURVEY.md 8(d) and reads its JSON line.  Columns follow mpi_results.csv
 (file, size_bytes, size_mb, backend, processes, time_seconds, sa_time,
@@ -36,7 +36,8 @@ COLUMNS = ["file", "size_bytes", "size_mb", "backend", "processes", "time_second
 
 def command(n_gpus, args, port):
     bench = [os.path.join(ROOT, "bench.py"), "--gpus", str(n_gpus), "--steps", str(args.steps), "--warmup",
-             str(args.warmup), "--n", str(args.n), "--kind", args.kind]
+             str(args.warmup), "--n", str(args.n), "--kind", args.kind,
+             "--full"]   # the O(n) check ("verified") and the CPU baseline are --full legs
     if n_gpus > 1 or args.no_cpu_baseline:
         bench.append("--no-cpu-baseline")
     if n_gpus == 1:

@@ -7,11 +7,11 @@
 #   pytest_fast  -m "gpu and not slow"
 #   k:<expr>     -m gpu -k <expr>
 #   smoke        __graft_entry__.smoke()
-#   bench        bench.py (1 GiB DNA, CPU baseline, reference schedule)
-#   bench_quick  bench.py without the CPU baseline and the reference schedule
-#   dist1        bench.py --mode distributed (the range-partitioned driver at N = 1)
-#   degenerate   bench.py --kind degenerate
-#   kinds        bench.py for alnum / ascii127 / byte256
+#   bench        bench.py --full (1 GiB DNA, CPU baseline, reference schedule)
+#   bench_quick  bench.py --full without the CPU baseline and the reference schedule
+#   dist1        bench.py --full --mode distributed (the range-partitioned driver at N = 1)
+#   degenerate   bench.py --full --kind degenerate
+#   kinds        bench.py --full for alnum / ascii127 / byte256
 
 #   collect      rocprof summaries: DNA, degenerate, reference schedule
 #   collect_dna  rocprof summary of the headline only
@@ -36,12 +36,12 @@ for s in "$@"; do
     pytest_fast) run 600 pytest_gpu_fast.log python -u -m pytest -v --timeout 200 --timeout-method thread -m "gpu and not slow" tests ;;
     k:*) e=${s#k:}; run 600 pytest_k.log python -u -m pytest -v --timeout 200 --timeout-method thread -m gpu -k "$e" tests ;;
     smoke) run 120 smoke.log python -u -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run 300 bench_dna1g.log python -u bench.py ;;
-    bench_quick) run 200 bench_quick.log python -u bench.py --no-cpu-baseline --no-reference-schedule ;;
-    dist1) run 300 bench_dist1.log python -u bench.py --mode distributed --no-cpu-baseline ;;
-    degenerate) run 300 bench_degenerate1g.log python -u bench.py --kind degenerate --no-cpu-baseline --no-reference-schedule ;;
+    bench) run 300 bench_dna1g.log python -u bench.py --full ;;
+    bench_quick) run 200 bench_quick.log python -u bench.py --full --no-cpu-baseline --no-reference-schedule ;;
+    dist1) run 300 bench_dist1.log python -u bench.py --full --mode distributed --no-cpu-baseline ;;
+    degenerate) run 300 bench_degenerate1g.log python -u bench.py --full --kind degenerate --no-cpu-baseline --no-reference-schedule ;;
     kinds) for k in alnum ascii127 byte256; do
-               run 200 bench_$k.log python -u bench.py --kind $k --no-cpu-baseline --no-reference-schedule
+               run 200 bench_$k.log python -u bench.py --full --kind $k --no-cpu-baseline --no-reference-schedule
            done ;;
 
     collect) run 900 collect_dna.log bash profiles/collect.sh ${tag} &&
@@ -50,7 +50,7 @@ for s in "$@"; do
     collect_dna) run 900 collect_dna.log bash profiles/collect.sh ${tag} ;;
     mb_bucket) run 120 mb_bucket.log hpc_suffix_array_amd/csrc/build/microbench_bucket 30 5 ;;
     alnumk) for kk in 8 7; do
-                run 200 bench_alnum_k$kk.log python -u bench.py --kind alnum --init-chars $kk --no-cpu-baseline --no-reference-schedule --no-lcp
+                run 200 bench_alnum_k$kk.log python -u bench.py --full --kind alnum --init-chars $kk --no-cpu-baseline --no-reference-schedule --no-lcp
             done ;;
     abcheck) run 300 ab_check.txt python -u scripts/ab_check.py 0 3 ;;
     abref:*) v=${s#abref:}; run 600 abref_${v//[,+]/_}.txt python -u scripts/ab_debug.py --schedule reference --reps 3 default ${v//,/ } ;;

@@ -145,6 +145,64 @@ def test_bench_picks_the_profile_of_the_current_sources(tmp_path):
     assert s is not None and s["tag"] != "r02_o"
 
 
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: a short SA is written whole; a longer one as
+    seeded sample positions, the entries there and block sums that cover
+    every entry -- float64, the same positions on every call, u32 positions
+    stored in int32 read back unsigned."""
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(7)
+    n = 1000
+    sa = torch.from_numpy(rng.permutation(n).astype(np.int32))
+    assert bench.dump_outputs(str(tmp_path / "w"), sa, n, torch) == {"sa.npy": n}
+    got = np.load(tmp_path / "w" / "sa.npy")
+    assert got.dtype == np.float64 and (got == sa.numpy()).all()
+    # the sampled form at a small size: 37 positions, 16 blocks of ceil(1003 / 16) = 63 (the last one short)
+    monkeypatch.setattr(bench, "DUMP_WHOLE_MAX", 100)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 37)
+    monkeypatch.setattr(bench, "DUMP_BLOCKS", 16)
+    n = 1003
+    v = rng.permutation(n).astype(np.int64)
+    v[5] = 0xFFFFFFF0   # above 2^31: negative as int32
+    sa = torch.from_numpy(v.astype(np.uint32).view(np.int32))
+    for d in ("a", "b"):
+        files = bench.dump_outputs(str(tmp_path / d), sa, n, torch)
+        assert files == {"sa_sample_pos.npy": 37, "sa_sample.npy": 37, "sa_block_sums.npy": 16}
+    a = {f: np.load(tmp_path / "a" / f) for f in files}
+    b = {f: np.load(tmp_path / "b" / f) for f in files}
+    assert all(a[f].dtype == np.float64 and (a[f] == b[f]).all() for f in files)
+    pos = a["sa_sample_pos.npy"].astype(np.int64)
+    assert (np.diff(pos) >= 0).all() and pos.min() >= 0 and pos.max() < n
+    assert (a["sa_sample.npy"] == v[pos]).all()
+    want = np.concatenate([v, np.zeros(16 * 63 - n, np.int64)]).reshape(16, 63).sum(1)
+    assert (a["sa_block_sums.npy"] == want).all() and want.sum() == v.sum()
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_and_dump(gpu, oracle, tmp_path):
+    """A plain bench.py run (no --full) times --steps builds, writes the last
+    one's SA with --dump-outputs -- the oracle's SA of the same seeded text
+    (--kind dna --seed 1), so the same files on every run --
+    and leaves the --full legs null."""
+    import json
+    n = 300_007
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--n", str(n), "--dump-outputs", str(tmp_path / "d")],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
+    assert line["steps"] == 3 and line["full"] is False and line["ms_per_step"] > 0
+    # value = n suffixes over one timed step; ms_per_step is printed rounded to 0.001 ms
+    assert abs(1e3 * n / line["value"] - line["ms_per_step"]) <= 0.00051
+    assert line["dumped_outputs"] == {"sa.npy": n}
+    for k in ("verified", "post_build", "reference_schedule", "cpu_baseline"):
+        assert line[k] is None, k
+    got = np.load(tmp_path / "d" / "sa.npy")
+    assert got.dtype == np.float64 and (got == oracle.sa_c(oracle.gen_text("dna", n, seed=1))).all()
+
+
 def test_reference_schedule_round_model():
     """bench.py's per-round roofline of the reference schedule follows
     SURVEY.md 8(d): P_j from D_{j-1} with D_0 = 256, B_j = n (3 rb + 2 S
@@ -179,6 +237,7 @@ def test_scaling_harness_columns_and_commands():
     assert one[1].endswith("bench.py") and "--no-cpu-baseline" not in one
     assert "torch.distributed.run" in two and "--master-addr" in two and "127.0.0.1" in two
     assert "--no-cpu-baseline" in two and two[two.index("--gpus") + 1] == "2"
+    assert "--full" in one and "--full" in two   # "verified" and "cpu_baseline" are --full legs of bench.py
     res = [(1, {"ms_per_step": 40.0, "value": 2.5e10, "cpu_baseline": {"value": 1e7}}),
            (2, {"ms_per_step": 25.0, "value": 4.0e10})]
     rows = S.rows_from(res, "dna_1073741824", 1 << 30)
