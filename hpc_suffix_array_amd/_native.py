@@ -27,6 +27,14 @@ ROUND1_AUTO = 0
 ROUND1_LSD = 1
 ROUND1_BUCKETED = 2
 SA_K_COUNT = len(KERNEL_KINDS)
+# sa_find_device flags (include/sa_hip.h SA_FIND_*) and the auto mode's length
+# threshold: patterns of up to FIND_LANE_MAX bytes are searched one per lane,
+# longer ones one per wavefront
+FIND_AUTO = 0
+FIND_LANE = 1
+FIND_WAVE = 2
+FIND_LANE_MAX = 3584
+FIND_MODES = {"auto": FIND_AUTO, "lane": FIND_LANE, "wave": FIND_WAVE}
 
 # every symbol include/*.h declares
 DROPIN_SYMBOLS = ["create_suffix_array", "destroy_suffix_array", "build_suffix_array",
@@ -36,6 +44,7 @@ EXT_SYMBOLS = ["sa_context_create", "sa_context_destroy", "sa_context_set_debug"
                "sa_alphabet_device", "sa_pack_keys_device", "sa_sort_pairs_device", "sa_scatter_u64_device",
                "sa_gather_u64_device", "sa_running_max_i64_device", "sa_inclusive_sum_i64_device",
                "sa_count_below_u64_device", "sa_select_u8_device",
+               "sa_find_device", "sa_find", "sa_find_ex",
                "sa_dist_begin", "sa_dist_cuts", "sa_dist_plan_cuts", "sa_dist_reserve", "sa_dist_release", "sa_dist_round1", "sa_dist_req_count", "sa_dist_req_fill",
                "sa_dist_answer", "sa_dist_refine",
                "sa_last_error", "sa_host_syncs", "sa_device_count", "sa_version", "sa_struct_size"]
@@ -216,6 +225,12 @@ def lib() -> ctypes.CDLL:
     L.sa_count_below_u64_device.restype = i32
     L.sa_select_u8_device.argtypes = [vp, u64, vp, ctypes.POINTER(u64), vp]
     L.sa_select_u8_device.restype = i32
+    L.sa_find_device.argtypes = [vp, u64, vp, vp, u64, vp, u64, vp, vp, ctypes.c_uint32, vp]
+    L.sa_find_device.restype = i32
+    L.sa_find.argtypes = [vp, u64, vp, i32, vp, vp, u64, vp, vp]
+    L.sa_find.restype = i32
+    L.sa_find_ex.argtypes = [vp, u64, vp, i32, vp, vp, u64, vp, vp, ctypes.c_uint32]
+    L.sa_find_ex.restype = i32
     DI = ctypes.POINTER(SaDistInfo)
     L.sa_dist_begin.argtypes = [vp, vp, u64, i32, i32, ctypes.POINTER(ctypes.c_uint32), vp, vp, DI]
     L.sa_dist_cuts.argtypes = [vp, ctypes.POINTER(u64), DI]

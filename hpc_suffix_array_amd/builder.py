@@ -120,6 +120,93 @@ def lcp_array(text, sa, width: int = 4):
     return out[:n], (int(ln.value), int(pos.value))
 
 
+def _pack_patterns(patterns):
+    """(buffer uint8, offsets uint64 of nq + 1) of a batch of patterns: a
+    sequence of bytes / str / uint8 arrays is concatenated; a
+    ``(buffer, offsets)`` pair (offsets: an integer numpy array that is not
+    uint8, or a list of ints) is taken as it is."""
+    if isinstance(patterns, tuple) and len(patterns) == 2:
+        o = patterns[1]
+        is_off = (isinstance(o, np.ndarray) and o.dtype.kind in "iu" and o.dtype != np.uint8) or (
+            isinstance(o, (list, tuple)) and all(isinstance(x, (int, np.integer)) for x in o))
+        if is_off:
+            off = np.asarray(o)
+            if off.ndim != 1 or off.size < 1:
+                raise ValueError("pattern offsets: one-dimensional, nq + 1 entries")
+            if off.dtype.kind == "i" and (off < 0).any():
+                raise ValueError("pattern offsets are negative")
+            buf = _as_bytes_array(patterns[0]).reshape(-1)
+            off = np.ascontiguousarray(off, dtype=np.uint64)
+            if int(off[-1]) > buf.size:
+                raise ValueError(f"pattern offsets end at {int(off[-1])}, the buffer holds {buf.size} bytes")
+            return buf, off
+    if isinstance(patterns, (bytes, bytearray, memoryview, str)):
+        raise TypeError("patterns: a sequence of patterns or a (buffer, offsets) pair, not one pattern")
+    parts = [_as_bytes_array(p).reshape(-1) for p in patterns]
+    off = np.zeros(len(parts) + 1, dtype=np.uint64)
+    if parts:
+        off[1:] = np.cumsum([p.size for p in parts], dtype=np.uint64)
+        buf = np.concatenate(parts) if int(off[-1]) else np.zeros(0, np.uint8)
+    else:
+        buf = np.zeros(0, np.uint8)
+    return np.ascontiguousarray(buf, dtype=np.uint8), off
+
+
+def _find_host(t_ptr, n: int, sa_ptr, width: int, patterns, mode: str):
+    """sa_find_ex over host pointers: (lo, hi) as int64 arrays."""
+    if mode not in N.FIND_MODES:
+        raise ValueError(f"mode {mode!r}: one of {sorted(N.FIND_MODES)}")
+    buf, off = _pack_patterns(patterns)
+    nq = int(off.size) - 1
+    lo = np.zeros(nq, dtype=np.uint64)
+    hi = np.zeros(nq, dtype=np.uint64)
+    if nq:
+        N.check(N.lib().sa_find_ex(t_ptr if n else None, n, sa_ptr if n else None, width,
+                                   buf.ctypes.data if buf.size else None, off.ctypes.data, nq,
+                                   lo.ctypes.data, hi.ctypes.data, N.FIND_MODES[mode]), "sa_find")
+    return lo.astype(np.int64), hi.astype(np.int64)
+
+
+def _text_and_sa(text, sa):
+    t = _as_bytes_array(text)
+    s = np.ascontiguousarray(sa)
+    if s.dtype not in (np.uint32, np.int32, np.int64):
+        s = s.astype(np.int64)
+    if s.size != t.size:
+        raise ValueError(f"SA has {s.size} entries for a text of {t.size} bytes")
+    return t, s
+
+
+def find_patterns(text, sa, patterns, mode: str = "auto"):
+    """SA intervals of a batch of patterns, searched on the GPU (sa_find).
+
+    ``sa`` is the suffix array of ``text``; ``patterns`` is a sequence of
+    bytes / str / uint8 arrays or a ``(buffer, offsets)`` pair with nq + 1
+    non-decreasing offsets.  Returns ``(lo, hi)``, two int64 arrays: pattern
+    q of m bytes occurs at the text positions ``sa[lo[q]:hi[q]]`` (SA order),
+    and ``lo[q] == hi[q]`` is its insertion point when it does not occur.
+    Unsigned-byte order, end of string smallest; binary-safe; the empty
+    pattern gives ``(0, n)``.  ``mode``: "auto", or "lane" / "wave" to force
+    one kernel for every pattern (tests, A/B runs)."""
+    t, s = _text_and_sa(text, sa)
+    N.require_device()
+    return _find_host(t.ctypes.data, int(t.size), s.ctypes.data, 8 if s.dtype == np.int64 else 4, patterns, mode)
+
+
+def count_patterns(text, sa, patterns, mode: str = "auto") -> np.ndarray:
+    """Occurrences of each pattern in ``text`` (int64): hi - lo of find_patterns."""
+    lo, hi = find_patterns(text, sa, patterns, mode)
+    return hi - lo
+
+
+def locate_patterns(text, sa, patterns, mode: str = "auto") -> list:
+    """Text positions of each pattern, ascending: the host slices
+    ``sa[lo:hi]`` of find_patterns, sorted."""
+    lo, hi = find_patterns(text, sa, patterns, mode)
+    s = np.asarray(sa)
+    return [np.sort(s[a:b].astype(np.int64)) for a, b in zip(lo.tolist(), hi.tolist())]
+
+
 class SuffixArray:
     """The reference's SuffixArray object (suffix_array.h:16-21) driven
     through the drop-in C symbols of libsa_hip.so.
@@ -156,6 +243,23 @@ class SuffixArray:
         if self.n > 0:
             N.require_device()
         return bool(self.L.is_valid_suffix_array(self.p))           # :184-202
+
+    def find(self, pattern, mode: str = "auto") -> tuple:
+        """(lo, hi): ``pattern`` occurs at ``sa[lo:hi]`` (sa_find at width 4
+        over the object's own str / sa; build() first)."""
+        N.require_device()
+        c = self.p.contents
+        lo, hi = _find_host(c.str, self.n, ctypes.cast(c.sa, ctypes.c_void_p).value, 4, [pattern], mode)
+        return int(lo[0]), int(hi[0])
+
+    def count(self, pattern) -> int:
+        lo, hi = self.find(pattern)
+        return hi - lo
+
+    def locate(self, pattern) -> np.ndarray:
+        """Text positions of ``pattern``, ascending."""
+        lo, hi = self.find(pattern)
+        return np.sort(self.sa[lo:hi].astype(np.int64))
 
     @property
     def text(self) -> bytes:
@@ -244,6 +348,19 @@ class DeviceBuilder:
         N.check(self.L.sa_lcp_device(self.ctx, self._ptr(d_text), n, self._ptr(d_sa), self._ptr(d_lcp),
                                      ctypes.byref(ln), ctypes.byref(pos), s), "sa_lcp_device")
         return int(ln.value), int(pos.value)
+
+    def find(self, d_text, n: int, d_sa, d_pat, pat_bytes: int, d_off, nq: int, d_lo, d_hi, stream=None,
+             mode: str = "auto") -> None:
+        """SA intervals of nq patterns, everything in HBM (sa_find_device):
+        pattern q is bytes d_off[q] .. d_off[q + 1] (uint64, nq + 1 entries) of
+        the pat_bytes at d_pat; [d_lo[q], d_hi[q]) (uint32) is its interval in
+        the SA at d_sa.  Enqueued on ``stream``; does not wait for it."""
+        if mode not in N.FIND_MODES:
+            raise ValueError(f"mode {mode!r}: one of {sorted(N.FIND_MODES)}")
+        s = None if stream is None else ctypes.c_void_p(int(stream))
+        N.check(self.L.sa_find_device(self._ptr(d_text), n, self._ptr(d_sa), self._ptr(d_pat), pat_bytes,
+                                      self._ptr(d_off), nq, self._ptr(d_lo), self._ptr(d_hi), N.FIND_MODES[mode], s),
+                "sa_find_device")
 
     def close(self) -> None:
         if self.ctx:

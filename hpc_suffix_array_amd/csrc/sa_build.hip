@@ -2164,6 +2164,10 @@ static int global_ctx(uint64_t n, sa_context** out) {
 
 }  // namespace sa
 
+// batched pattern search (sa_find, sa_find_device): kernels, launches and its
+// entry points
+#include "sa_find.h"
+
 using namespace sa;
 
 extern "C" {

@@ -195,6 +195,48 @@ int sa_lcp_device(sa_context* ctx, const uint8_t* d_text, uint64_t n, const uint
 int sa_lcp(const uint8_t* text, uint64_t n, const void* sa, int sa_width, void* lcp_out, uint64_t* lrs_len,
            uint64_t* lrs_pos);
 
+/* ---- batched exact-match search over a built suffix array ---------------
+ * (the reference has no search; csrc/sa_find.h).  Order is the builder's:
+ * unsigned bytes, end of string smallest.  Pattern q is the m = off[q+1] -
+ * off[q] bytes at pat + off[q]; its interval [lo, hi) holds the SA positions
+ * r with SA[r] + m <= n and text[SA[r] .. SA[r] + m) equal to it.  A suffix
+ * shorter than m that is a proper prefix of the pattern sorts below it; when
+ * nothing matches lo == hi is the insertion point.  The empty pattern gives
+ * [0, n), n == 0 gives [0, 0), m > n an empty interval.  Binary-safe: 0x00
+ * and 0xFF are ordinary bytes, lengths are explicit.  The count is hi - lo,
+ * the occurrences are SA[lo .. hi) in SA order (not text order). */
+
+/* flags: 0 auto (patterns of up to SA_FIND_LANE_MAX bytes by one lane each,
+ * longer ones by one wavefront each), SA_FIND_LANE one query per lane for
+ * every pattern, SA_FIND_WAVE one query per wavefront for every pattern
+ * (tests, A/B). */
+#define SA_FIND_LANE 1u
+#define SA_FIND_WAVE 2u
+#define SA_FIND_LANE_MAX 3584   /* the measured crossover of the two kernels */
+
+/* d_text: n bytes, d_sa: n uint32, d_pat: pat_bytes bytes, d_pat_off: nq + 1
+ * uint64, d_lo / d_hi: nq uint32, all in device memory; n <= 2^32 - 1.
+ * Asynchronous on `stream` (no host wait, no workspace); SA_OK without a
+ * launch when nq == 0.
+ * Preconditions: d_sa is a valid suffix array of the text, and the offsets
+ * are non-decreasing and end at or below pat_bytes.  When they do not hold
+ * the results are unspecified, but no load leaves the three buffers: an
+ * SA[r] >= n reads as the empty suffix, offsets are clamped to pat_bytes and
+ * a decreasing pair is the empty pattern. */
+int sa_find_device(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa,
+                   const uint8_t* d_pat, uint64_t pat_bytes, const uint64_t* d_pat_off /* nq+1 */,
+                   uint64_t nq, uint32_t* d_lo, uint32_t* d_hi, uint32_t flags, void* stream);
+/* Host in, host out: sa has width sa_width (4 or 8; width-8 entries outside
+ * [0, n) are SA_E_INVALID), pat_off holds nq + 1 non-decreasing offsets into
+ * pat (SA_E_INVALID otherwise).  Allocates, uses and frees device buffers. */
+int sa_find(const uint8_t* text, uint64_t n, const void* sa, int sa_width,
+            const uint8_t* pat, const uint64_t* pat_off, uint64_t nq,
+            uint64_t* lo_out, uint64_t* hi_out);
+/* sa_find with the flags of sa_find_device (tests, A/B) */
+int sa_find_ex(const uint8_t* text, uint64_t n, const void* sa, int sa_width,
+               const uint8_t* pat, const uint64_t* pat_off, uint64_t nq,
+               uint64_t* lo_out, uint64_t* hi_out, uint32_t flags);
+
 /* ---- building blocks of the range-partitioned multi-GPU build ----------
  * (hpc_suffix_array_amd/distributed.py drives these per rank; the exchange
  * steps between them are RCCL collectives over xGMI.)                      */
@@ -285,13 +327,13 @@ int sa_dist_begin(sa_context* ctx, const uint8_t* d_text, uint64_t n, int world,
                   const uint32_t present[8], uint64_t* d_coarse, void* stream, sa_dist_info* info);
 /* h_coarse: the all-reduced coarse histogram on the host (NULL at world 1) */
 int sa_dist_cuts(sa_context* ctx, const uint64_t* h_coarse, sa_dist_info* info);
-/* Frees the range-partitioned build's per-rank buffers of ctx (rank and
- * member arrays, request buffers); the context stays usable (a fallback
- * driver reuses its workspace).  Synchronises the device first. */
 /* Allocate ahead of the first build everything a range build of up to
  * max_n symbols over `world` ranks needs (sa_dist_cuts would otherwise do it
  * inside the first build). */
 int sa_dist_reserve(sa_context* ctx, uint64_t max_n, int world);
+/* Frees the range-partitioned build's per-rank buffers of ctx (rank and
+ * member arrays, request buffers); the context stays usable (a fallback
+ * driver reuses its workspace).  Synchronises the device first. */
 int sa_dist_release(sa_context* ctx);
 /* The cut plan sa_dist_cuts applies (host only, no device): world + 1 cuts
  * into the 4096 coarse buckets of h_coarse (summing to n) at bucket width
