@@ -365,6 +365,65 @@ __global__ __launch_bounds__(kSpBlock) void k_split(Src src, uint64_t n, uint32_
 #ifndef SA_TEXT_FULL
 #define SA_TEXT_FULL 1
 #endif
+// The four switches below restructure the pass's staging, scan and write
+// loop.  1 GiB DNA, interleaved on one box: the parent 2.85 ms, all four
+// 2.76; with one off: LOAD16 2.89, SCAN1 2.78, TAB1 3.10, EARLY 2.87; LOAD16
+// + SCAN1 alone 2.83, LOAD16 alone 2.84, EARLY alone 2.91
+// (profiles/r07_a_ab_text_parts.txt: the parts gain together, not one by one).
+// SA_TEXT_LOAD16: the tile + halo is fetched as aligned 16-byte chunks, one
+// per lane (lanes 0 .. NW / 4 - 1), instead of four strided 4-byte words; the
+// lane maps its four words and stages them with ONE LDS store (DNA: the four
+// packed bytes as one s_pkw word -- the byte stores of lanes w .. w + 3 hit
+// one bank -- and no s_dcw at all, which only the other variants read;
+// others: one 16-byte s_dcw store).  A text that is not 16-byte aligned and
+// the tiles whose chunks cross n take the 4-byte loads into the same
+// registers.
+#ifndef SA_TEXT_LOAD16
+#define SA_TEXT_LOAD16 1
+#endif
+// SA_TEXT_SCAN1: the 256 digit counts are scanned by wave 0 alone, four
+// consecutive digits per lane straight from s_cnt (one 16-byte read, one DPP
+// scan, one 8-byte s_start store): no wave totals through s_tmp and no
+// barrier between their write and read.  s_cnt is then cleared after the
+// scan's barrier (wave 0 reads the other waves' digits).
+#ifndef SA_TEXT_SCAN1
+#define SA_TEXT_SCAN1 1
+#endif
+// SA_TEXT_TAB1: the write loop reads ONE table word per item, s_gofs[d] =
+// the digit's global place minus its tile-local start (mod 2^32; an item's
+// place is the word + its LDS slot), instead of s_gofs, s_start and the bound
+// (s_gend or m).  The bound is tested once per digit and tile where the
+// claim returns: a run that does not fit sets `over` as before and its word
+// becomes kTabSkip, which the item loop compares (none of the run's items is
+// stored; the round re-runs).  Places are below 2^32 - 1 (n <= 2^32 - 1), so
+// a fitting run's word equals kTabSkip = ~0 only when its place is one below
+// its tile-local start: never with exact digit bases (a digit's base is at
+// least the tile's count of the digits before it), and under padded
+// segments such a run counts as not fitting (the round re-runs exactly).
+#ifndef SA_TEXT_TAB1
+#define SA_TEXT_TAB1 1
+#endif
+// SA_TEXT_EARLY: the next tile is staged (s_pkw / s_dcw, the ticket after
+// it) between the LDS scatter's barrier and the write loop instead of at
+// the top of its own iteration: the staged arrays are read in the key loop
+// only, three barriers earlier, and the end-of-tile barrier closes the
+// staging too (no barrier of its own; the first tile is staged before the
+// loop).  The wait for the text words then stands before this tile's stores
+// are issued, not behind them.
+#ifndef SA_TEXT_EARLY
+#define SA_TEXT_EARLY 1
+#endif
+// SA_TEXT_TPT: tiles per ticket -- thread 0 takes up to SA_TEXT_TPT
+// consecutive tiles with one atomic on the ticket counter (every workgroup's
+// tickets go to one address: 175 k returning atomics at 1 GiB DNA).  Only
+// where a workgroup has 128 tiles or more to take (half as many per ticket
+// from 32), so that a ticket stays a few percent of a workgroup's work at
+// most and the tail of the launch as short as it was.
+// 1 GiB DNA: 1 tile per ticket 2.73 ms, 2: 2.68, 4: 2.67, 8: 2.67-2.73
+// (profiles/r07_b_ab_text_tickets.txt).
+#ifndef SA_TEXT_TPT
+#define SA_TEXT_TPT 4
+#endif
 // IDENT (sigma = 256, every byte present, K <= 8): the dense digit is the
 // byte itself -- staged without the byte map, and each position's D and
 // remainder are bit fields of the big-endian 8-byte window at it (two
@@ -403,19 +462,26 @@ __global__ __launch_bounds__(BLOCK, 2048 / BLOCK) void k_split_text(const uint8_
     constexpr int NW = (TILE + kHalo) / 4;              // staged text words
     constexpr int WPT = (NW + BLOCK - 1) / BLOCK; // per lane
     static_assert(ITEMS % 4 == 0 && kHalo % 4 == 0 && TILE <= 65535, "word staging, 16-bit tile offsets");
+    constexpr bool LD16 = SA_TEXT_LOAD16 != 0, SCAN1 = SA_TEXT_SCAN1 != 0, TAB1 = SA_TEXT_TAB1 != 0;
+    constexpr bool EARLY = SA_TEXT_EARLY != 0;
+    constexpr int NC = NW / 4;                          // LD16: staged 16-byte chunks, one per lane
+    static_assert(!LD16 || (NW % 4 == 0 && NC <= BLOCK && WPT <= 4), "one 16-byte chunk per lane");
+    static_assert(!SCAN1 || RADIX == 4 * kWave, "wave 0 scans four digits per lane");
     __shared__ uint64_t s_keys[TILE];
     __shared__ uint16_t s_idx[TILE];                    // tile offset; PK8: the pair's digit
-    __shared__ uint32_t s_dcw[NW + 8];                  // dense digits, 4 per word (0 past the end; + slack)
+    // dense digits, 4 per word (0 past the end; + slack); not staged by DNA under LD16
+    __shared__ __attribute__((aligned(16))) uint32_t s_dcw[(DNA && LD16) ? 4 : NW + 8];
     // DNA: the digits packed 2 bits each, one byte per staged word (the first
     // digit on top), so a lane's 32 symbols from l0 are three word reads and
     // each position's key1 a shift of that window (no Horner start, no
     // per-position byte extraction); the host launches it when K + ITEMS - 1 <= 32
     __shared__ uint32_t s_pkw[DNA ? (NW + 3) / 4 + 4 : 1];
     __shared__ uint8_t s_map[256];
-    __shared__ uint32_t s_cnt[RADIX];
-    __shared__ uint16_t s_start[RADIX];
-    __shared__ uint32_t s_gofs[RADIX];
-    __shared__ uint32_t s_tmp[RWAVES];
+    __shared__ __attribute__((aligned(16))) uint32_t s_cnt[RADIX];
+    __shared__ __attribute__((aligned(8))) uint16_t s_start[RADIX];
+    constexpr uint32_t kTabSkip = ~0u;
+    __shared__ uint32_t s_gofs[RADIX];   // TAB1: digit d's global place minus s_start[d], or kTabSkip
+    __shared__ uint32_t s_tmp[RWAVES];   // (unused under SCAN1)
     __shared__ uint32_t s_tile[2];
     __shared__ uint32_t s_kept;
     __shared__ uint32_t s_hhi[1024];   // the second pass's digit totals (local bucket >> kLoBits)
@@ -442,7 +508,28 @@ __global__ __launch_bounds__(BLOCK, 2048 / BLOCK) void k_split_text(const uint8_
         s_map[dg] = (uint8_t)(cv ? cv - 1u : 0u);
     }
     if (dg < (uint32_t)RADIX) s_cnt[dg] = 0;
-    if (dg == 0) s_tile[0] = atomicAdd(ticket, 1u);
+    // thread 0: the next tile of its ticket and the tiles left in it
+    constexpr uint32_t TPT = SA_TEXT_TPT;
+    static_assert(TPT >= 1 && (TPT & (TPT - 1)) == 0, "tiles per ticket: a power of two");
+    // (the same for every workgroup: the counter counts tickets)
+    const uint32_t tpt = tiles >= 128ull * gridDim.x ? TPT : tiles >= 32ull * gridDim.x && TPT > 1 ? TPT / 2 : 1u;
+    uint32_t tk_tile = 0, tk_left = 0;
+    auto next_tile = [&]() -> uint32_t {
+        if constexpr (TPT == 1) {
+            return atomicAdd(ticket, 1u);
+        } else {
+            if (tk_left == 0) {
+                tk_tile = atomicAdd(ticket, 1u) * tpt;
+                tk_left = tpt;
+            }
+            --tk_left;
+            return tk_tile++;
+        }
+    };
+    if (dg == 0) {
+        s_tile[0] = next_tile();
+        if constexpr (EARLY) s_tile[1] = next_tile();   // (iteration i takes tile i + 2's)
+    }
     __syncthreads();
     uint64_t t = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_tile[0]);
     // raw text words dg, dg + 1024, ... of the tile + halo; bytes at or past
@@ -454,23 +541,38 @@ __global__ __launch_bounds__(BLOCK, 2048 / BLOCK) void k_split_text(const uint8_
             if (pos + q < n) w |= (uint32_t)text[pos + q] << (8 * q);
         return w;
     };
-    uint32_t raw[WPT];
-    auto load = [&](uint64_t tt) {
-        const uint64_t tb = tt * TILE;
-#pragma unroll
-        for (int i = 0; i < WPT; ++i) {
-            // words past NW (unused) re-read word NW - 1: no zero written
-            // into a register a load may still be filling
-            const uint32_t w = dg + i * BLOCK;
-            raw[i] = load4(tb + 4ull * (w < (uint32_t)NW ? w : (uint32_t)NW - 1u));
-        }
-    };
-    if (t < tiles) load(t);
-    uint32_t par = 0;
     // tile-level range tests as 32-bit tile-index compares (scalar): in 64
     // bits they went to VALU with a hoisted 64-bit constant that spilled to
     // scratch, and every reload waited for the previous tile's stores
     const uint32_t t_whole = n >= 4ull * NW ? (uint32_t)((n - 4ull * NW) / TILE + 1) : 0u;   // tb + 4 NW <= n
+    // LD16: raw = the lane's chunk, text words 4 dg .. 4 dg + 3 of the tile
+    uint32_t raw[LD16 ? 4 : WPT];
+    const bool al16 = (((uintptr_t)text) & 15) == 0;   // uniform (a tile starts at a multiple of 16)
+    auto load = [&](uint64_t tt) {
+        const uint64_t tb = tt * TILE;
+        if constexpr (LD16) {
+            // chunks past NC (unused) re-read chunk NC - 1: no zero written
+            // into a register a load may still be filling
+            const uint64_t cb = tb + 16ull * (dg < (uint32_t)NC ? dg : (uint32_t)NC - 1u);
+            if (al16 && (uint32_t)tt < t_whole) {   // every chunk inside the text
+                const uint4 v = *reinterpret_cast<const uint4*>(text + cb);
+                raw[0] = v.x, raw[1] = v.y, raw[2] = v.z, raw[3] = v.w;
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) raw[i] = load4(cb + 4ull * i);
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < WPT; ++i) {
+                // words past NW (unused) re-read word NW - 1: no zero written
+                // into a register a load may still be filling
+                const uint32_t w = dg + i * BLOCK;
+                raw[i] = load4(tb + 4ull * (w < (uint32_t)NW ? w : (uint32_t)NW - 1u));
+            }
+        }
+    };
+    if (t < tiles) load(t);
+    uint32_t par = 0;
     const uint32_t t_int = n >= (uint64_t)TILE + K ? (uint32_t)((n - TILE - K) / TILE + 1) : 0u;   // tb + TILE + K <= n
     const uint32_t t_last = (uint32_t)(tiles - 1);
 #if SA_TEXT_PROF
@@ -485,13 +587,49 @@ __global__ __launch_bounds__(BLOCK, 2048 / BLOCK) void k_split_text(const uint8_
 #else
 #define TEXT_STAMP(k)
 #endif
-    while (t < tiles) {
-        const uint64_t tb = t * TILE;
-        const uint32_t valid = (uint32_t)t < t_last ? (uint32_t)TILE : (uint32_t)(n - tb);
+    // stages tile tt from raw
+    auto stage = [&](uint64_t tt) {
+        const uint64_t tb = tt * TILE;
         // dense digits (0 past the end); a tile whose staged words lie inside
         // the text maps its four bytes with four independent LDS reads (the
         // per-byte bounds test made them a chain of branches and waits)
-        const bool whole = (uint32_t)t < t_whole;   // uniform
+        const bool whole = (uint32_t)tt < t_whole;   // uniform
+        if constexpr (LD16) {
+            if (dg < (uint32_t)NC) {
+                uint32_t o[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    o[i] = 0;
+                    if (whole) {
+                        if constexpr (DNA)
+                            o[i] = ((raw[i] >> 1) ^ (raw[i] >> 2)) & 0x03030303u;
+                        else if constexpr (IDENT)
+                            o[i] = raw[i];
+                        else
+                            o[i] = (uint32_t)s_map[raw[i] & 0xFFu] | ((uint32_t)s_map[(raw[i] >> 8) & 0xFFu] << 8) |
+                                   ((uint32_t)s_map[(raw[i] >> 16) & 0xFFu] << 16) |
+                                   ((uint32_t)s_map[raw[i] >> 24] << 24);
+                    } else {
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) {
+                            const uint64_t pos = tb + 16ull * dg + 4ull * i + q;
+                            o[i] |= (pos < n ? (uint32_t)s_map[(raw[i] >> (8 * q)) & 0xFFu] : 0u) << (8 * q);
+                        }
+                    }
+                }
+                if constexpr (DNA) {
+                    // byte i = the packed byte of text word 4 dg + i
+                    uint32_t pw = 0;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        pw |= ((((o[i] & 3u) << 6) | ((o[i] >> 4) & 0x30u) | ((o[i] >> 14) & 0xCu) | (o[i] >> 24)) & 0xFFu)
+                              << (8 * i);
+                    s_pkw[dg] = pw;
+                } else {
+                    *reinterpret_cast<uint4*>(&s_dcw[4 * dg]) = make_uint4(o[0], o[1], o[2], o[3]);
+                }
+            }
+        } else {
 #pragma unroll
         for (int i = 0; i < WPT; ++i) {
             const uint32_t w = dg + i * BLOCK;
@@ -518,11 +656,24 @@ __global__ __launch_bounds__(BLOCK, 2048 / BLOCK) void k_split_text(const uint8_
                         (uint8_t)(((o & 3u) << 6) | ((o >> 4) & 0x30u) | ((o >> 14) & 0xCu) | (o >> 24));
             }
         }
-        // the next tile's ticket now: its round trip overlaps this tile's key
-        // computation (no look-back depends on the ticket order); its text
-        // loads wait until after the claims (loading right here was slower)
-        if (dg == 0) s_tile[par ^ 1u] = atomicAdd(ticket, 1u);
+        }
+    };
+    if constexpr (EARLY) {
+        if (t < tiles) stage(t);
         __syncthreads();
+    }
+    while (t < tiles) {
+        const uint64_t tb = t * TILE;
+        const uint32_t valid = (uint32_t)t < t_last ? (uint32_t)TILE : (uint32_t)(n - tb);
+        if constexpr (!EARLY) {
+            stage(t);
+            // the next tile's ticket now: its round trip overlaps this tile's
+            // key computation (no look-back depends on the ticket order); its
+            // text loads wait until after the claims (loading right here was
+            // slower)
+            if (dg == 0) s_tile[par ^ 1u] = next_tile();
+            __syncthreads();
+        }
         TEXT_STAMP(0)
         // key1 of positions tb + ITEMS dg + j (D < 64 sigma 2^bb <= 2^32 rolls
         // in 32 bits; the remainder in 64)
@@ -632,14 +783,24 @@ __global__ __launch_bounds__(BLOCK, 2048 / BLOCK) void k_split_text(const uint8_
             uint32_t dgo = dg;
             asm volatile("" : "+v"(dgo));
             tile_cnt = s_cnt[dgo];
-            s_cnt[dgo] = 0;
+            if constexpr (!SCAN1) s_cnt[dgo] = 0;
             // the pass need not be stable, so a tile's place in each digit
             // is claimed from a cursor (one atomic round trip, whatever the
             // other tiles do) instead of a look-back
             dbase = seg_end ? sbase : digit_base[dgo];
             clm = tile_cnt ? atomicAdd(&cursor[dgo], tile_cnt) : 0u;
         }
-        {
+        if constexpr (SCAN1) {
+            if (wave == 0) {
+                // digits 4 lane .. 4 lane + 3: their counts, the scan of the
+                // lanes' sums, four 16-bit starts as one store
+                const uint4 c4 = *reinterpret_cast<const uint4*>(&s_cnt[4 * lane]);
+                const uint32_t inc = wave_inclusive_sum(c4.x + c4.y + c4.z + c4.w);
+                const uint32_t e0 = inc - (c4.x + c4.y + c4.z + c4.w), e1 = e0 + c4.x, e2 = e1 + c4.y, e3 = e2 + c4.z;
+                *reinterpret_cast<uint2*>(&s_start[4 * lane]) = make_uint2(e0 | (e1 << 16), e2 | (e3 << 16));
+                if (lane == kWave - 1) s_kept = inc;   // pairs kept in this tile
+            }
+        } else {
             const uint32_t x = (dg < (uint32_t)RADIX) ? tile_cnt : 0u;
             const uint32_t inc = wave_inclusive_sum(x);
             if (lane == kWave - 1 && wave < (uint32_t)RWAVES) s_tmp[wave] = inc;
@@ -653,6 +814,13 @@ __global__ __launch_bounds__(BLOCK, 2048 / BLOCK) void k_split_text(const uint8_
         // the next tile's text loads
         __syncthreads();
         TEXT_STAMP(2)
+        if constexpr (SCAN1) {
+            if (dg < (uint32_t)RADIX) {
+                uint32_t dgo = dg;
+                asm volatile("" : "+v"(dgo));
+                s_cnt[dgo] = 0;
+            }
+        }
         const uint64_t tn = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_tile[par ^ 1u]);
         load(tn < tiles ? tn : tiles - 1);
         // PK8: the item is built here, not in the key loop (its extra live
@@ -696,9 +864,32 @@ __global__ __launch_bounds__(BLOCK, 2048 / BLOCK) void k_split_text(const uint8_
         }
         // the claims' round trips overlapped the staging (only the writes
         // need the tile's places)
-        if (dg < (uint32_t)RADIX) s_gofs[dg] = dbase + clm;
+        if constexpr (TAB1) {
+            if (dg < (uint32_t)RADIX) {
+                // the digit's run [g0, g0 + tile_cnt) against its bound, once
+                uint32_t dgo = dg;
+                asm volatile("" : "+v"(dgo));
+                const uint64_t g0 = (uint64_t)dbase + clm;
+                const uint64_t gend = seg_end ? (uint64_t)s_gend[dgo] : m;
+                const uint32_t gw = (uint32_t)g0 - s_start[dgo];
+                const bool fits = g0 + tile_cnt <= gend && gw != kTabSkip;
+                if (tile_cnt && !fits) over = true;
+                s_gofs[dgo] = fits ? gw : kTabSkip;
+            }
+        } else {
+            if (dg < (uint32_t)RADIX) s_gofs[dg] = dbase + clm;
+        }
         __syncthreads();
         TEXT_STAMP(3)
+        if constexpr (EARLY) {
+            // the next tile staged now, the ticket of the one after it
+            // requested before the wait for the text words
+            uint32_t tk;
+            if (dg == 0) tk = next_tile();
+            if (tn < tiles) stage(tn);
+            if (dg == 0) s_tile[par] = tk;
+            TEXT_STAMP(0)
+        }
         const uint32_t kept = s_kept;
 #pragma unroll
         for (int j = 0; j < ITEMS; ++j) {
@@ -714,12 +905,21 @@ __global__ __launch_bounds__(BLOCK, 2048 / BLOCK) void k_split_text(const uint8_
                                              : (uint32_t)(((key >> b.rb) * b.cmul) >> b.bsh);
                     dd = (bq - blo) & (RADIX - 1);
                 }
-                const uint64_t g = (uint64_t)s_gofs[dd] + (q - s_start[dd]);
-                if (seg_end ? g < s_gend[dd] : g < m) {
-                    out_keys[g] = key;
-                    if constexpr (!PK8) out_vals[g] = (uint32_t)(tb + s_idx[q]);
+                if constexpr (TAB1) {
+                    const uint32_t gw = s_gofs[dd];
+                    if (gw != kTabSkip) {
+                        const uint32_t g = gw + q;
+                        out_keys[g] = key;
+                        if constexpr (!PK8) out_vals[g] = (uint32_t)(tb + s_idx[q]);
+                    }
                 } else {
-                    over = true;
+                    const uint64_t g = (uint64_t)s_gofs[dd] + (q - s_start[dd]);
+                    if (seg_end ? g < s_gend[dd] : g < m) {
+                        out_keys[g] = key;
+                        if constexpr (!PK8) out_vals[g] = (uint32_t)(tb + s_idx[q]);
+                    } else {
+                        over = true;
+                    }
                 }
             }
         }
