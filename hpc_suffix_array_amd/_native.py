@@ -59,7 +59,7 @@ class SAError(RuntimeError):
 DEBUG_FLAGS = {"no_cmp": 0x1, "no_pk8": 0x2, "no_pad": 0x4, "pad_overflow": 0x8, "no_fast32": 0x10,
                "no_pivot": 0x20, "perm_always": 0x40, "no_xq": 0x80, "xq_overflow": 0x100,
                "no_tied": 0x200, "no_key1_round": 0x400, "no_eonly": 0x800,
-               "eonly": 0x1000}
+               "eonly": 0x1000, "fast32_small": 0x2000}
 
 
 def debug_bits(names) -> int:
@@ -102,6 +102,7 @@ class SaStats(ctypes.Structure):
         ("round1_segments", ctypes.c_int32),
         ("round1_layout", ctypes.c_int32),
         ("round_bytes", ctypes.c_uint64 * SA_MAX_ROUNDS),
+        ("round1_windows", ctypes.c_int32 * 4),
     ]
 
     def to_dict(self) -> dict:
@@ -128,6 +129,9 @@ class SaStats(ctypes.Structure):
                               "xq": bool(self.round1_layout & 4), "eonly": bool(self.round1_layout & 8)},
             "reference_model_bytes": int(self.model_bytes),
             "round_bytes": [int(x) for x in self.round_bytes[:r]],
+            # bucketed round 1: non-empty windows, one-bucket windows of the fixed-span kernel, windows
+            # sorted again with the measured span, skewed windows (first local-sort launch)
+            "round1_windows": [int(x) for x in self.round1_windows],
             "kernels": {k: {"ms": self.kern_ms[i], "launches": int(self.kern_launches[i]),
                             "bytes": int(self.kern_bytes[i])} for i, k in enumerate(KERNEL_KINDS)},
         }

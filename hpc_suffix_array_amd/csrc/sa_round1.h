@@ -408,8 +408,12 @@ static int round1_bucketed(sa_context* c, const uint8_t* d_text, uint64_t n, uin
     // windows hold one bucket each (suffixes per bucket of the range >= 4
     // window strides; a rank's range holds m suffixes in bhi - blo buckets --
     // m >> bb undercounted them by G, and ranges took k_bucket_sort_wide)
+    // (the size term is a heuristic: windows of several buckets take the
+    // measured-span launch whatever the average; SA_DEBUG_FAST32_SMALL drops
+    // it so tests reach the kernel at sizes a CPU oracle sorts)
     const bool fast32 = bits1 > (uint32_t)kSubBits && bits1 - kSubBits <= kLowMax &&
-                        m / (uint64_t)(bhi - blo) >= 4ull * kWinStride && !(c->dbg & SA_DEBUG_NO_FAST32);
+                        (m / (uint64_t)(bhi - blo) >= 4ull * kWinStride || (c->dbg & SA_DEBUG_FAST32_SMALL)) &&
+                        !(c->dbg & SA_DEBUG_NO_FAST32);
     // the second pass by per-XCD queues and regions (sa_split.h SegXq): the
     // fixed-span local sort (which loads a one-bucket window's 8 chunks), a
     // grid of whole XCDs, the regions' slack in keys_u (ensure_u_capacity:
@@ -810,8 +814,12 @@ static int round1_bucketed(sa_context* c, const uint8_t* d_text, uint64_t n, uin
     }
     tm.end();
     SA_HIP(hipGetLastError());
-    SA_HIP(hipMemcpyAsync(c->host_words, c->words, 44, hipMemcpyDeviceToHost, s));
+    SA_HIP(hipMemcpyAsync(c->host_words, c->words, 64, hipMemcpyDeviceToHost, s));
     SA_HIP(host_sync(s));
+    if (st) {   // where the first launch sent the windows (the dense re-run below recounts words 13-15)
+        const uint32_t wv[4] = {c->host_words[7], c->host_words[kHdrWord], c->host_words[kRetryWord], c->host_words[10]};
+        for (int t = 0; t < 4; ++t) st->round1_windows[t] = (int32_t)std::min<uint32_t>(wv[t], INT32_MAX);
+    }
     if (c->host_words[6]) {
         SA_TRACE("  bucketed round 1: local sort flags %u, full sort instead", c->host_words[6]);
         return SA_OK;

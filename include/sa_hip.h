@@ -99,6 +99,9 @@ enum sa_kernel_kind {
                                            first-pass items) instead of the E-only layout that packs them */
 #define SA_DEBUG_EONLY 0x1000u          /* bucketed round 1: the E-only key1 layout whenever the text's tail allows
                                            it (tests; production takes it only for packed non-power-of-two items) */
+#define SA_DEBUG_FAST32_SMALL 0x2000u   /* local sort: the fixed-span 32-bit kernel whenever the key span allows it,
+                                           whatever the average bucket size (tests: reaches it below 2^28 suffixes;
+                                           windows of several buckets still take the measured-span kernel) */
 
 typedef struct {
     int32_t profile;        /* 1: time every launch with HIP events */
@@ -153,6 +156,10 @@ typedef struct {
                                             key1 low (no end bit; non-power-of-two alphabets' PK8) */
     uint64_t round_bytes[SA_MAX_ROUNDS]; /* algorithmic bytes of the kernels launched in round j (the kern_bytes
                                             added between its boundaries; the schedule actually run) */
+    int32_t round1_windows[4];           /* bucketed round 1, the local sort's first launch: [0] non-empty windows,
+                                            [1] one-bucket windows sorted by the fixed-span kernel, [2] windows
+                                            sorted again with their measured span (several buckets, or keys
+                                            clustered in one sub-bucket), [3] skewed windows (LSD kernel) */
 } sa_stats;
 
 typedef struct sa_context sa_context;

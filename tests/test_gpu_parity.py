@@ -992,12 +992,15 @@ def test_round1_xq_second_pass(gpu):
 
 @pytest.mark.parametrize("extra", [0, 6])
 def test_local_sort_fixed_span(gpu, oracle, extra):
-    """One-bucket windows of the compact layout split the bucket's whole key
-    span into sub-buckets without measuring it (sa_bucket.h load_window,
-    SA_LS_FIXED_SPAN); a window whose keys cluster (forced here by a span 2^6
-    too wide: every key in the lowest sub-buckets) is listed for a second
-    launch that measures its span (sa_round1.h, retry list) instead of going
-    to the LSD kernel."""
+    """The measured-span kernel (sa_bucket.h k_bucket_sort_wide, load_window)
+    given the compact layout's fixed span: at these sizes the average bucket
+    is far below four window strides, so the fixed-span 32-bit kernel
+    (k_bucket_sort; tests/test_gpu_local_sort.py) never runs here.  One-bucket
+    windows split the bucket's whole key span into sub-buckets without
+    measuring it; a window whose keys cluster (forced here by a span 2^6 too
+    wide: every key in the lowest sub-buckets) is listed for a second launch
+    that measures its span (sa_round1.h, retry list) instead of going to the
+    LSD kernel."""
     from hpc_suffix_array_amd import build_suffix_array
     for kind, n in (("dna", 3_000_017), ("byte256", 1 << 21)):
         t = oracle.gen_text(kind, n, seed=n + 5)
