@@ -45,6 +45,7 @@ EXT_SYMBOLS = ["sa_context_create", "sa_context_destroy", "sa_context_set_debug"
                "sa_gather_u64_device", "sa_running_max_i64_device", "sa_inclusive_sum_i64_device",
                "sa_count_below_u64_device", "sa_select_u8_device",
                "sa_find_device", "sa_find", "sa_find_ex",
+               "sa_match_device", "sa_matching_stats_device", "sa_match", "sa_matching_stats",
                "sa_dist_begin", "sa_dist_cuts", "sa_dist_plan_cuts", "sa_dist_reserve", "sa_dist_release", "sa_dist_round1", "sa_dist_req_count", "sa_dist_req_fill",
                "sa_dist_answer", "sa_dist_refine",
                "sa_last_error", "sa_host_syncs", "sa_device_count", "sa_version", "sa_struct_size"]
@@ -235,6 +236,14 @@ def lib() -> ctypes.CDLL:
     L.sa_find.restype = i32
     L.sa_find_ex.argtypes = [vp, u64, vp, i32, vp, vp, u64, vp, vp, ctypes.c_uint32]
     L.sa_find_ex.restype = i32
+    L.sa_match_device.argtypes = [vp, u64, vp, vp, u64, vp, u64, vp, vp, vp, ctypes.c_uint32, vp]
+    L.sa_match_device.restype = i32
+    L.sa_matching_stats_device.argtypes = [vp, u64, vp, vp, u64, u64, vp, vp, vp, ctypes.c_uint32, vp]
+    L.sa_matching_stats_device.restype = i32
+    L.sa_match.argtypes = [vp, u64, vp, i32, vp, vp, u64, vp, vp, vp, ctypes.c_uint32]
+    L.sa_match.restype = i32
+    L.sa_matching_stats.argtypes = [vp, u64, vp, i32, vp, u64, u64, vp, vp, vp, ctypes.c_uint32]
+    L.sa_matching_stats.restype = i32
     DI = ctypes.POINTER(SaDistInfo)
     L.sa_dist_begin.argtypes = [vp, vp, u64, i32, i32, ctypes.POINTER(ctypes.c_uint32), vp, vp, DI]
     L.sa_dist_cuts.argtypes = [vp, ctypes.POINTER(u64), DI]

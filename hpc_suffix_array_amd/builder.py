@@ -207,6 +207,69 @@ def locate_patterns(text, sa, patterns, mode: str = "auto") -> list:
     return [np.sort(s[a:b].astype(np.int64)) for a, b in zip(lo.tolist(), hi.tolist())]
 
 
+def _match_host(t_ptr, n: int, sa_ptr, width: int, patterns, mode: str, bounds: bool):
+    """sa_match over host pointers: (length, lo, hi) as int64 arrays, or the
+    lengths alone."""
+    if mode not in N.FIND_MODES:
+        raise ValueError(f"mode {mode!r}: one of {sorted(N.FIND_MODES)}")
+    buf, off = _pack_patterns(patterns)
+    nq = int(off.size) - 1
+    out = np.zeros((3 if bounds else 1, nq), dtype=np.uint64)
+    if nq:
+        N.check(N.lib().sa_match(t_ptr if n else None, n, sa_ptr if n else None, width,
+                                 buf.ctypes.data if buf.size else None, off.ctypes.data, nq, out[0].ctypes.data,
+                                 out[1].ctypes.data if bounds else None, out[2].ctypes.data if bounds else None,
+                                 N.FIND_MODES[mode]), "sa_match")
+    out = out.astype(np.int64)
+    return (out[0], out[1], out[2]) if bounds else out[0]
+
+
+def match_patterns(text, sa, patterns, mode: str = "auto", bounds: bool = True):
+    """Longest match of each pattern of a batch, searched on the GPU (sa_match).
+
+    ``text``, ``sa``, ``patterns`` and ``mode`` are those of find_patterns.
+    Returns ``(length, lo, hi)``, three int64 arrays: ``length[q]`` is the
+    largest l for which the first l bytes of pattern q occur in ``text``, and
+    that prefix occurs at the text positions ``sa[lo[q]:hi[q]]``.  A pattern
+    that occurs whole gets its find_patterns interval; ``length == 0`` (the
+    empty pattern, a first byte the text does not hold) gives ``(0, n)``.
+    ``bounds=False`` returns the lengths alone and skips the two bound
+    searches."""
+    t, s = _text_and_sa(text, sa)
+    N.require_device()
+    return _match_host(t.ctypes.data, int(t.size), s.ctypes.data, 8 if s.dtype == np.int64 else 4, patterns, mode,
+                       bounds)
+
+
+def matching_statistics(text, sa, query, max_len: int = 0, mode: str = "auto", bounds: bool = True):
+    """Matching statistics of ``query`` against ``text`` on the GPU
+    (sa_matching_stats): one longest-match query per position of ``query``.
+
+    Entry i answers ``query[i:]`` (``query[i:i + max_len]`` when ``max_len``
+    is not 0) as match_patterns would: ``(length, lo, hi)``, int64 arrays of
+    ``len(query)`` entries, or the lengths alone with ``bounds=False``.
+    ``mode``: "auto" takes the one-query-per-lane kernel when no query can be
+    longer than FIND_LANE_MAX bytes and the one-query-per-wavefront kernel
+    otherwise; "lane" / "wave" force one."""
+    if mode not in N.FIND_MODES:
+        raise ValueError(f"mode {mode!r}: one of {sorted(N.FIND_MODES)}")
+    if max_len < 0:
+        raise ValueError("max_len is negative")
+    t, s = _text_and_sa(text, sa)
+    N.require_device()
+    q = _as_bytes_array(query).reshape(-1)
+    n, m = int(t.size), int(q.size)
+    out = np.zeros((3 if bounds else 1, m), dtype=np.uint64)
+    if m:
+        N.check(N.lib().sa_matching_stats(t.ctypes.data if n else None, n, s.ctypes.data if n else None,
+                                          8 if s.dtype == np.int64 else 4, q.ctypes.data, m, int(max_len),
+                                          out[0].ctypes.data, out[1].ctypes.data if bounds else None,
+                                          out[2].ctypes.data if bounds else None, N.FIND_MODES[mode]),
+                "sa_matching_stats")
+    out = out.astype(np.int64)
+    return (out[0], out[1], out[2]) if bounds else out[0]
+
+
 class SuffixArray:
     """The reference's SuffixArray object (suffix_array.h:16-21) driven
     through the drop-in C symbols of libsa_hip.so.
@@ -251,6 +314,15 @@ class SuffixArray:
         c = self.p.contents
         lo, hi = _find_host(c.str, self.n, ctypes.cast(c.sa, ctypes.c_void_p).value, 4, [pattern], mode)
         return int(lo[0]), int(hi[0])
+
+    def longest_match(self, pattern, mode: str = "auto") -> tuple:
+        """(length, lo, hi): the first ``length`` bytes of ``pattern`` are its
+        longest prefix that occurs in the text, at ``sa[lo:hi]`` (sa_match at
+        width 4 over the object's own str / sa; build() first)."""
+        N.require_device()
+        c = self.p.contents
+        ln, lo, hi = _match_host(c.str, self.n, ctypes.cast(c.sa, ctypes.c_void_p).value, 4, [pattern], mode, True)
+        return int(ln[0]), int(lo[0]), int(hi[0])
 
     def count(self, pattern) -> int:
         lo, hi = self.find(pattern)
@@ -361,6 +433,39 @@ class DeviceBuilder:
         N.check(self.L.sa_find_device(self._ptr(d_text), n, self._ptr(d_sa), self._ptr(d_pat), pat_bytes,
                                       self._ptr(d_off), nq, self._ptr(d_lo), self._ptr(d_hi), N.FIND_MODES[mode], s),
                 "sa_find_device")
+
+    def match(self, d_text, n: int, d_sa, d_pat, pat_bytes: int, d_off, nq: int, d_len, d_lo=None, d_hi=None,
+              stream=None, mode: str = "auto") -> None:
+        """Longest match of nq patterns, everything in HBM (sa_match_device):
+        the patterns are given as for find; d_len[q] (uint32) is the length of
+        pattern q's longest prefix that occurs in the text and
+        [d_lo[q], d_hi[q]) that prefix's interval in the SA at d_sa.
+        ``d_lo=None, d_hi=None`` asks for the lengths only.  Enqueued on
+        ``stream``; does not wait for it."""
+        if mode not in N.FIND_MODES:
+            raise ValueError(f"mode {mode!r}: one of {sorted(N.FIND_MODES)}")
+        s = None if stream is None else ctypes.c_void_p(int(stream))
+        N.check(self.L.sa_match_device(self._ptr(d_text), n, self._ptr(d_sa), self._ptr(d_pat), pat_bytes,
+                                       self._ptr(d_off), nq, self._ptr(d_len),
+                                       None if d_lo is None else self._ptr(d_lo),
+                                       None if d_hi is None else self._ptr(d_hi), N.FIND_MODES[mode], s),
+                "sa_match_device")
+
+    def matching_statistics(self, d_text, n: int, d_sa, d_query, m: int, d_len, d_lo=None, d_hi=None,
+                            max_len: int = 0, stream=None, mode: str = "auto") -> None:
+        """Matching statistics of the m bytes at d_query against the text,
+        everything in HBM (sa_matching_stats_device): entry i of d_len, d_lo
+        and d_hi (uint32, m entries each) answers d_query[i : i + max_len]
+        (to the end when max_len is 0) as match does.  ``d_lo=None,
+        d_hi=None`` asks for the lengths only.  Enqueued on ``stream``; does
+        not wait for it."""
+        if mode not in N.FIND_MODES:
+            raise ValueError(f"mode {mode!r}: one of {sorted(N.FIND_MODES)}")
+        s = None if stream is None else ctypes.c_void_p(int(stream))
+        N.check(self.L.sa_matching_stats_device(self._ptr(d_text), n, self._ptr(d_sa), self._ptr(d_query), m, max_len,
+                                                self._ptr(d_len), None if d_lo is None else self._ptr(d_lo),
+                                                None if d_hi is None else self._ptr(d_hi), N.FIND_MODES[mode], s),
+                "sa_matching_stats_device")
 
     def close(self) -> None:
         if self.ctx:

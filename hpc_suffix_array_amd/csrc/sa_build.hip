@@ -2167,6 +2167,8 @@ static int global_ctx(uint64_t n, sa_context** out) {
 // batched pattern search (sa_find, sa_find_device): kernels, launches and its
 // entry points
 #include "sa_find.h"
+// longest-match queries and matching statistics over the same search core
+#include "sa_match.h"
 
 using namespace sa;
 

@@ -244,6 +244,47 @@ int sa_find_ex(const uint8_t* text, uint64_t n, const void* sa, int sa_width,
                const uint8_t* pat, const uint64_t* pat_off, uint64_t nq,
                uint64_t* lo_out, uint64_t* hi_out, uint32_t flags);
 
+/* ---- longest-match queries and matching statistics ----------------------
+ * (csrc/sa_match.h).  Order and byte handling are sa_find's.  For a query P
+ * of m bytes against the n bytes of the text, len is the largest l <= m for
+ * which P[0 .. l) occurs in the text, and [lo, hi) is the sa_find interval of
+ * P[0 .. len): an occurrence of the match is SA[lo], all of them are
+ * SA[lo .. hi).  len == m gives exactly what sa_find gives for P; len == 0
+ * gives [0, n) (m == 0, or a first byte the text does not hold); n == 0 gives
+ * len 0 and [0, 0).
+ * The batch form takes nq patterns as sa_find does.  The sliding form takes
+ * one string of m bytes and answers for each of its positions i the query
+ * string[i .. min(m, i + max_len)) (max_len == 0: to the string's end): with
+ * max_len == 0 that is the matching statistics of the string against the
+ * text, m entries in each output.
+ * d_lo / d_hi (lo_out / hi_out) are both given or both NULL; both NULL asks
+ * for the lengths only and skips the two bound searches; one of them NULL is
+ * SA_E_INVALID.
+ * flags: 0, SA_FIND_LANE or SA_FIND_WAVE.  0 splits the batch form's patterns
+ * by length at SA_FIND_LANE_MAX as sa_find does; for the sliding form, whose
+ * positions all have one cap, 0 takes the lane kernel when no query can be
+ * longer than SA_FIND_LANE_MAX bytes (1 <= max_len <= SA_FIND_LANE_MAX, or
+ * m <= SA_FIND_LANE_MAX) and the wave kernel otherwise.
+ * The device forms are asynchronous on `stream` (no host wait, no workspace)
+ * and return SA_OK without a launch when there are no queries; n <= 2^32 - 1;
+ * outputs are uint32.  Preconditions and what holds without them: as for
+ * sa_find_device (results unspecified, no load leaves the buffers, every
+ * search ends).  The host forms allocate, use and free device buffers and
+ * check their arguments as sa_find does. */
+int sa_match_device(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa,
+                    const uint8_t* d_pat, uint64_t pat_bytes, const uint64_t* d_pat_off /* nq+1 */,
+                    uint64_t nq, uint32_t* d_len, uint32_t* d_lo, uint32_t* d_hi, uint32_t flags, void* stream);
+int sa_matching_stats_device(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa,
+                             const uint8_t* d_query, uint64_t m, uint64_t max_len /* 0 = none */,
+                             uint32_t* d_len, uint32_t* d_lo, uint32_t* d_hi /* m entries each */,
+                             uint32_t flags, void* stream);
+int sa_match(const uint8_t* text, uint64_t n, const void* sa, int sa_width,
+             const uint8_t* pat, const uint64_t* pat_off, uint64_t nq,
+             uint64_t* len_out, uint64_t* lo_out, uint64_t* hi_out, uint32_t flags);
+int sa_matching_stats(const uint8_t* text, uint64_t n, const void* sa, int sa_width,
+                      const uint8_t* query, uint64_t m, uint64_t max_len,
+                      uint64_t* len_out, uint64_t* lo_out, uint64_t* hi_out, uint32_t flags);
+
 /* ---- building blocks of the range-partitioned multi-GPU build ----------
  * (hpc_suffix_array_amd/distributed.py drives these per rank; the exchange
  * steps between them are RCCL collectives over xGMI.)                      */
