@@ -1083,6 +1083,120 @@ __global__ __launch_bounds__(kBlock) void k_u_gather(const uint32_t* __restrict_
     }
 }
 
+// Round 2 of a one-GPU build straight from the local sort's staging, without
+// the compacted set, key buffer, ranks or segments pass: a round-1 group lies
+// inside one window, its members are consecutive there (so.tmp_*, window-local
+// group ids) and occupy consecutive SA positions, and its round-2 key is
+// key1(x + K) + 1 from the text (0 past the end; SrcUKey1).  Each member takes
+// the count of its group's smaller keys as its rank and writes SA[group start
+// + rank].  One wave takes kR2Batch listed windows per step (their headers one
+// per lane) and packs as many whole windows as fit its 64 lanes into a pass.
+// *flag is set, and nothing of the window written, when the round cannot
+// finish the build this way: a window of more than 64 members, a group of more
+// than kUsLimit, two equal keys in a group (still tied after 2K symbols), or
+// staging that does not fit this build.  The caller then runs the set through
+// k_wscan_* + k_u_gather and the general rounds, which rewrite every member's
+// SA entry; the writes made here before the failure only permute entries
+// inside round-1 groups.  cnt_u is read unscanned.
+// Every index is bounded by what the kernel loaded: members per window <= 64,
+// staging slot < m, x < n, SA position < m.
+constexpr int kR2Batch = 16;
+
+__global__ __launch_bounds__(kBlock) void k_round2_windows(const uint32_t* __restrict__ list, const uint32_t* words,
+                                                           const uint32_t* __restrict__ ws,
+                                                           const uint32_t* __restrict__ cnt_u,
+                                                           const uint32_t* __restrict__ tmp_pos,
+                                                           const uint32_t* __restrict__ tmp_idx,
+                                                           const uint32_t* __restrict__ tmp_g,
+                                                           const uint8_t* __restrict__ text, uint64_t n,
+                                                           const uint16_t* __restrict__ code, BucketSpec bs, uint64_t m,
+                                                           uint32_t* __restrict__ sa, uint32_t* flag) {
+    const uint32_t nlist = words[7];
+    const uint32_t lane = lane_id();
+    const uint32_t K = bs.s + bs.R;
+    const CodeMap map{code};
+    const uint64_t lt = lanemask_lt(), lem = lt | (1ull << lane);
+    for (uint64_t q0 = ((uint64_t)blockIdx.x * kWaves + wave_id()) * kR2Batch; q0 < nlist;
+         q0 += (uint64_t)gridDim.x * kWaves * kR2Batch) {
+        if (__builtin_amdgcn_readfirstlane((int)__atomic_load_n(flag, __ATOMIC_RELAXED))) return;
+        uint32_t a_l = 0, c_l = 0;
+        if (lane < (uint32_t)kR2Batch && q0 + lane < nlist) {
+            const uint32_t j = list[q0 + lane];
+            c_l = cnt_u[j];
+            a_l = ws[j];
+        }
+        if (__ballot(c_l > (uint32_t)kWave)) {
+            if (lane == 0) atomicOr(flag, 1u);
+            return;
+        }
+        const uint32_t e_l = wave_inclusive_sum(c_l);   // <= kR2Batch * 64
+        uint64_t todo = __ballot(c_l != 0);
+        uint32_t base = 0;   // members of the windows already done
+        while (todo) {       // uniform
+            // this pass: the longest prefix of the remaining windows whose
+            // members fit the wave (at least one: c <= 64)
+            const uint64_t fit = todo & __ballot(e_l - base <= (uint32_t)kWave);
+            todo &= ~fit;
+            uint32_t a = 0, off = 0, nbase = base;
+            bool act = false;
+            for (uint64_t f = fit; f; f &= f - 1) {
+                const int w = __builtin_ctzll(f);
+                const uint32_t ew = (uint32_t)__shfl((int)e_l, w, kWave), cw = (uint32_t)__shfl((int)c_l, w, kWave);
+                const uint32_t aw = (uint32_t)__shfl((int)a_l, w, kWave);
+                const uint32_t s0 = ew - cw - base;   // the window's first lane
+                if (lane >= s0 && lane < s0 + cw) {
+                    a = aw;
+                    off = lane - s0;
+                    act = true;
+                }
+                nbase = ew;
+            }
+            base = nbase;
+            bool bad = act && (uint64_t)a + off >= m;
+            act = act && !bad;
+            uint32_t pos = 0, x = 0, g = 0;
+            if (act) {
+                pos = tmp_pos[a + off];
+                x = tmp_idx[a + off];
+                g = tmp_g[a + off];
+            }
+            bad = bad || (act && x >= n);
+            uint64_t key = 0;
+            if (act && !bad && (uint64_t)x + K < n) {
+                uint32_t D;
+                key = key1_words<true>(text, n, map, bs, (uint64_t)x + K, &D) + 1u;
+            }
+            // group extents: a head where the window or its group id changes
+            const uint64_t ma = __ballot(act);
+            const uint32_t gp = (uint32_t)__shfl_up((int)g, 1, kWave);
+            const bool head = act && (lane == 0 || off == 0 || g != gp || !((ma >> (lane - 1)) & 1ull));
+            const uint64_t mh = __ballot(head);
+            const uint64_t hl = mh & lem, ab = (mh | ~ma) & ~lem;
+            const uint32_t start = hl ? 63u - (uint32_t)__clzll(hl) : lane;
+            const uint32_t end = ab ? (uint32_t)__builtin_ctzll(ab) : (uint32_t)kWave;
+            const uint32_t len = end - start;
+            bad = bad || (act && len > (uint32_t)kUsLimit);
+            uint32_t rank = 0;
+#pragma unroll
+            for (int t = 0; t < kUsLimit; ++t) {
+                const uint32_t src = (start + t) & (kWave - 1);
+                const uint64_t kk = __shfl(key, (int)src, kWave);
+                if (act && (uint32_t)t < len && src != lane) {
+                    rank += kk < key ? 1u : 0u;
+                    bad = bad || kk == key;
+                }
+            }
+            const uint64_t p = (uint64_t)(uint32_t)__shfl((int)pos, (int)start, kWave) + rank;
+            bad = bad || (act && p >= m);
+            if (__ballot(bad)) {
+                if (lane == 0) atomicOr(flag, 1u);
+                return;
+            }
+            if (act) sa[p] = x;
+        }
+    }
+}
+
 // Exclusive popcount scan of a bitmap of nw words (the compact rank map's
 // prefix, RankMap): k_popc_reduce (per-block popcount sums) -> k_popc_top
 // (their exclusive scan, one workgroup) -> k_popc_apply (each block's words

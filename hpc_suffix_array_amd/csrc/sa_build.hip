@@ -74,6 +74,11 @@ static hipError_t host_sync(hipStream_t s) {
     g_host_syncs.fetch_add(1, std::memory_order_relaxed);
     return hipStreamSynchronize(s);
 }
+// a wait for the work up to an event: what was enqueued behind it runs on
+static hipError_t host_sync_event(hipEvent_t e) {
+    g_host_syncs.fetch_add(1, std::memory_order_relaxed);
+    return hipEventSynchronize(e);
+}
 static hipError_t host_memcpy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
     g_host_syncs.fetch_add(1, std::memory_order_relaxed);
     return hipMemcpy(dst, src, bytes, kind);
@@ -111,6 +116,7 @@ static_assert(kMaxChunks >= 1 && kMaxChunks <= (1u << 20), "chunk scratch sized 
 constexpr uint64_t kSparseDiv = 8;
 constexpr int kEvPool = 256;
 constexpr int kRoundEv = SA_MAX_ROUNDS + 1;   // round boundary events (Timer::round_mark)
+constexpr int kSyncEv = kEvPool + kRoundEv;   // recorded behind a read-back the host waits for (host_sync_event)
 
 static uint64_t align_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
 
@@ -170,7 +176,7 @@ struct sa_context {
     uint16_t* code = nullptr;      // 256 byte -> dense code 1..sigma
     uint32_t* host_words = nullptr;  // pinned (4096 words): 64 words, 256 counts, 128 words of codes at 320, the text tail (64 B) at 2048,
                                      // per-rank counts of the range-partitioned build at 1024
-    hipEvent_t ev[sa::kEvPool + sa::kRoundEv];   // Timer pairs, then the round boundaries
+    hipEvent_t ev[sa::kEvPool + sa::kRoundEv + 1];   // Timer pairs, the round boundaries, a read-back (kSyncEv)
     int ev_ready = 0;
     sa::DistState* dist = nullptr;   // range-partitioned build state (sa_dist.h)
     // sa_opts debug / tune fields of the current build (sa_build_device's
@@ -375,6 +381,11 @@ struct Timer {
             mark_bytes[nr] = b;
         }
         ++nr;
+    }
+    // withdraw the last mark (the round it closed goes on after all); the
+    // next round_mark records its event again
+    void round_unmark() {
+        if (nr > 0) --nr;
     }
     void round_times() {
         const int last = std::min(nr, kRoundEv) - 1;
@@ -1101,7 +1112,6 @@ constexpr uint64_t kUsAvg = 4;
 #ifndef SA_US_TWO_PHASE
 #define SA_US_TWO_PHASE 1
 #endif
-constexpr int kUsFlagWord = 12;
 
 template <class Pos>
 static int segments(sa_context* c, const uint64_t* keys, const uint32_t* idx, const Chunking& ch, Pos pos,
@@ -1469,9 +1479,11 @@ static int build_packed(sa_context* c, const uint8_t* d_text, uint64_t n, uint32
     bool r1_pivot = false;   // round 1 by the pivot split (pivot_round1)
     uint64_t D = 0, m = 0, G = 0;
     uint64_t seg1[3] = {0, 0, 0};
+    int r2 = 0;   // round 2 from the local sort's staging (round1_bucketed): 1 gave up, 2 finished the build
     if (bucketed) {
         bool done = false;
-        rc = round1_bucketed(c, d_text, n, d_sa, bp, full_range(bp, n), s, tm, st, &done, &fused, seg1, &ksh1);
+        rc = round1_bucketed(c, d_text, n, d_sa, bp, full_range(bp, n), s, tm, st, &done, &fused, seg1, &ksh1, true,
+                             true, &r2);
         if (rc) return rc;
         bucketed = done;
         if (done) {
@@ -1548,10 +1560,21 @@ static int build_packed(sa_context* c, const uint8_t* d_text, uint64_t n, uint32
         add_bytes(st, SA_K_SORT_U, 12 * ns);
         return SA_OK;
     };
-    tm.round_mark();
+    if (r2 == 0) tm.round_mark();   // (else made before the round-2 kernel)
     record_round(st, 0.f, D, P, n, K);
     SA_TRACE("  round 1: D=%llu unsorted=%llu groups=%llu", (unsigned long long)D, (unsigned long long)m,
              (unsigned long long)G);
+    if (r2 == 2) {
+        // round 2 ordered every group by its next K symbols, no two members
+        // tied: the SA is complete
+        tm.round_mark();
+        D = n;
+        record_round(st, 0.f, D, 1, m, 2 * (uint64_t)K);
+        SA_TRACE("  round h=%u: sorted %llu from the local sort's staging, D=%llu", K, (unsigned long long)m,
+                 (unsigned long long)D);
+        m = 0;
+        G = 0;
+    }
 
     // doubling rounds over the unsorted set only
     const uint32_t wr = bit_width(n);   // rank values 0..n
@@ -1570,14 +1593,7 @@ static int build_packed(sa_context* c, const uint8_t* d_text, uint64_t n, uint32
         // ranks as key1 of x + K from the text (SrcUKey1) when group id and
         // key1 + 1 fit 64 bits
         uint32_t kb1 = 0;
-        if (bucketed && sparse && h == K && !(c->dbg & SA_DEBUG_NO_KEY1_ROUND)) {
-            unsigned __int128 dmax = 1;
-            for (uint32_t t = 0; t < bp.bs.s; ++t) dmax *= bp.bs.sigma;
-            const unsigned __int128 kmax = ((dmax - 1) << bp.bs.rb) | (((unsigned __int128)1 << bp.bs.rb) - 1);
-            uint32_t kw = 0;
-            for (unsigned __int128 x = kmax + 1; x; x >>= 1) ++kw;
-            kb1 = kw;
-        }
+        if (bucketed && sparse && h == K && !(c->dbg & SA_DEBUG_NO_KEY1_ROUND)) kb1 = key1_bits(bp.bs);
         const bool key1_round = kb1 > 0 && kb1 + wg <= 64;
         if (c->radix == 0 && G > 0 && m <= kUsAvg * G) {
             // small groups on average: sort each group in registers, unless
@@ -2215,7 +2231,7 @@ int sa_context_create(int device, uint64_t max_n, sa_context** out) {
         sa_context_destroy(c);
         return set_err(SA_E_NOMEM, "context allocation failed");
     }
-    for (int i = 0; i < kEvPool + kRoundEv; ++i) {
+    for (int i = 0; i < kEvPool + kRoundEv + 1; ++i) {
         if (hipEventCreate(&c->ev[i]) != hipSuccess) {
             sa_context_destroy(c);
             return set_err(SA_E_HIP, "hipEventCreate failed");

@@ -90,6 +90,19 @@ __global__ __launch_bounds__(kLoRadix) void k_sum_rows(const uint32_t* __restric
     out[threadIdx.x] = t;
 }
 constexpr uint64_t kPadMaxN = 1ull << 31;
+// words[]: set by a per-group register sort that cannot finish its round
+// (k_usort_small: a group over kUsLimit; k_round2_windows)
+constexpr int kUsFlagWord = 12;
+
+// bits of key1 + 1, the round-2 key of SrcUKey1 and k_round2_windows
+static uint32_t key1_bits(const BucketSpec& bs) {
+    unsigned __int128 dmax = 1;
+    for (uint32_t t = 0; t < bs.s; ++t) dmax *= bs.sigma;
+    const unsigned __int128 kmax = ((dmax - 1) << bs.rb) | (((unsigned __int128)1 << bs.rb) - 1);
+    uint32_t kw = 0;
+    for (unsigned __int128 x = kmax + 1; x; x >>= 1) ++kw;
+    return kw;
+}
 constexpr uint32_t kPadStartOff = kLoRadix + 1024;                 // kLoRadix + 1 words
 constexpr uint32_t kPadDenseOff = kPadStartOff + kLoRadix + 64;    // kLoRadix words
 
@@ -256,12 +269,20 @@ static uint32_t range_hb(uint32_t nb) {
 // the unsorted set only (member bitmap), the unsorted set compacted in
 // u_pos/u_idx/u_g[0], and seg = {D, m, G}; otherwise the caller runs
 // segments() on keys[0].
+// round2 (non-null: the caller can take it; one GPU): round 2 is tried
+// straight from the local sort's staging (k_round2_windows) behind the
+// round-1 boundary mark.  *round2 = 2: it finished the build (the SA is
+// complete; the set was not compacted); 1: it gave up and the set was
+// compacted as usual, the mark stays; 0: not run, or round 1 goes on in the
+// caller (the mark withdrawn).
 static int round1_bucketed(sa_context* c, const uint8_t* d_text, uint64_t n, uint32_t* d_sa, const BucketPlan& bp,
                            const BucketRange& br_, hipStream_t s, Timer& tm, sa_stats* st, bool* done, bool* fused,
-                           uint64_t seg[3], uint32_t* ksh, bool allow_pad = true, bool allow_xq = true) {
+                           uint64_t seg[3], uint32_t* ksh, bool allow_pad = true, bool allow_xq = true,
+                           int* round2 = nullptr) {
     *done = false;
     *fused = false;
     *ksh = 0;
+    if (round2) *round2 = 0;
     const uint64_t m = br_.m;   // suffixes of this range (= n on one GPU)
     const uint32_t blo = br_.blo, bhi = br_.bhi;
     if (bhi <= blo || bhi - blo > (1u << 18)) return set_err(SA_E_INTERNAL, "bucket range [%u, %u)", blo, bhi);
@@ -361,7 +382,7 @@ static int round1_bucketed(sa_context* c, const uint8_t* d_text, uint64_t n, uin
                 SA_TRACE("  bucketed round 1: a record stripe overflowed, again with the counting scan");
                 tm.end();
                 const int rc = round1_bucketed(c, d_text, n, d_sa, bp, br_, s, tm, st, done, fused, seg, ksh, false,
-                                               allow_xq);
+                                               allow_xq, round2);
                 if (st) st->round1_segments = 4;
                 return rc;
             }
@@ -648,29 +669,39 @@ static int round1_bucketed(sa_context* c, const uint8_t* d_text, uint64_t n, uin
     add_bytes(st, SA_K_WINDOWS, 8 * nw);
     SA_HIP(hipGetLastError());
     SA_HIP(hipMemcpyAsync(c->host_words, c->words, 48, hipMemcpyDeviceToHost, s));
-    SA_HIP(host_sync(s));
-    if (c->host_words[4]) return set_err(SA_E_INTERNAL, "radix look-back did not complete");
-    if (padded && c->host_words[11]) {   // a digit outgrew its sampled segment: exact totals
-        SA_TRACE("  bucketed round 1: padded segment overflow, again with exact digit totals");
-        const int rc = round1_bucketed(c, d_text, n, d_sa, bp, br_, s, tm, st, done, fused, seg, ksh, false, allow_xq);
-        if (st) st->round1_segments = 2;
-        return rc;
-    }
-    if (xq && c->host_words[9]) {   // a queue's digit outgrew its sub-region: one region
-        SA_TRACE("  bucketed round 1: second-pass queue overflow, again with one region");
-        return round1_bucketed(c, d_text, n, d_sa, bp, br_, s, tm, st, done, fused, seg, ksh, allow_pad, false);
-    }
-    if (st) st->largest_window = (int32_t)std::min<uint32_t>(c->host_words[5], INT32_MAX);
-    if (c->host_words[5] > (uint32_t)kBsCap) {
-        SA_TRACE("  bucketed round 1: window of %u > %d suffixes, full sort instead", c->host_words[5], kBsCap);
-        return SA_OK;
-    }
     // windows with clustered keys, then per-window U / U-group counts (scanned
     // in place: nw + 1 each), then each window's first bucket (nw + 1,
     // written by k_window_starts_tab); 6 nw + 4 <= capacity
     uint32_t* skew = list + nw;
     uint32_t* cnt_u = skew + nw;
     uint32_t* cnt_g = cnt_u + nw + 1;
+    uint32_t* const rank_arr = br_.rank ? br_.rank : c->rank;
+    uint32_t* const member = br_.member ? br_.member : c->member;
+    // the local sort's clears depend on nothing that is read back: enqueued
+    // behind the copy, they run while the host, which waits for the copy
+    // alone, turns around (a round that re-runs or falls back clears again)
+    SA_HIP(hipEventRecord(c->ev[kSyncEv], s));
+    SA_HIP(hipMemsetAsync(cnt_u, 0, (2 * nw + 2) * 4, s));
+    SA_HIP(hipMemsetAsync(member, 0, (n + 31) / 32 * 4, s));
+    SA_HIP(host_sync_event(c->ev[kSyncEv]));
+    if (c->host_words[4]) return set_err(SA_E_INTERNAL, "radix look-back did not complete");
+    if (padded && c->host_words[11]) {   // a digit outgrew its sampled segment: exact totals
+        SA_TRACE("  bucketed round 1: padded segment overflow, again with exact digit totals");
+        const int rc = round1_bucketed(c, d_text, n, d_sa, bp, br_, s, tm, st, done, fused, seg, ksh, false, allow_xq,
+                                       round2);
+        if (st) st->round1_segments = 2;
+        return rc;
+    }
+    if (xq && c->host_words[9]) {   // a queue's digit outgrew its sub-region: one region
+        SA_TRACE("  bucketed round 1: second-pass queue overflow, again with one region");
+        return round1_bucketed(c, d_text, n, d_sa, bp, br_, s, tm, st, done, fused, seg, ksh, allow_pad, false,
+                               round2);
+    }
+    if (st) st->largest_window = (int32_t)std::min<uint32_t>(c->host_words[5], INT32_MAX);
+    if (c->host_words[5] > (uint32_t)kBsCap) {
+        SA_TRACE("  bucketed round 1: window of %u > %d suffixes, full sort instead", c->host_words[5], kBsCap);
+        return SA_OK;
+    }
     BucketRel br{cnt_g + nw + 1, c->segw + kBstartOff, c->segw + kBstartOff + kBstartWords, bp.bs.rb};
     // the local sort's sub-buckets split a one-bucket window's whole key span
     // (D values per bucket x 2^rb) when the compact layout fills it; also for
@@ -678,10 +709,6 @@ static int round1_bucketed(sa_context* c, const uint8_t* d_text, uint64_t n, uin
     // local sort 7.05 / 6.85 ms with measured spans, 4.75 / 4.56 with the
     // fixed one: profiles/r02_av_ab_kinds_fixed_span_pow2_only.txt)
     br.bits1 = bits1;
-    SA_HIP(hipMemsetAsync(cnt_u, 0, (2 * nw + 2) * 4, s));
-    uint32_t* const rank_arr = br_.rank ? br_.rank : c->rank;
-    uint32_t* const member = br_.member ? br_.member : c->member;
-    SA_HIP(hipMemsetAsync(member, 0, (n + 31) / 32 * 4, s));
     // sorted key1 sampled (every 2^kKeySample-th SA position) for the sparse
     // rank look-ups; a round that turns out dense re-runs the sort with every
     // key1 below (segments() reads them all)
@@ -708,7 +735,9 @@ static int round1_bucketed(sa_context* c, const uint8_t* d_text, uint64_t n, uin
     auto local_sort = [&](const SegOut& o) {
         const uint32_t g = std::max<uint32_t>(1, std::min(c->host_words[7], kBsGrid));
         // (no SA_HIP here: its error return would make the lambda non-void)
-        (void)hipMemsetAsync(c->words + kRetryWord, 0, 12, s);   // retry count, one-bucket windows, ticket
+        // round-2 flag, retry count, one-bucket windows, ticket
+        static_assert(kRetryWord == kUsFlagWord + 1, "one memset clears words[12..15]");
+        (void)hipMemsetAsync(c->words + kUsFlagWord, 0, 16, s);
         if (fast32) {
             const uint32_t gs = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((nw + kBlock - 1) / kBlock, 1024));
             // XQ chunk rows (sa_bucket.h load_items_cr; tune bit 29: the
@@ -783,11 +812,9 @@ static int round1_bucketed(sa_context* c, const uint8_t* d_text, uint64_t n, uin
     tm.end();
     add_bytes(st, SA_K_LOCAL_SORT, 12 * m + (so.samples ? (m >> kKeySample) * 8 : 0));
     SA_HIP(hipGetLastError());
-    // the unsorted set, in SA order, compacted before the counts are read
-    // back (its launches overlap that round trip; a round that turns out
-    // dense, or falls back, ignores it: segments() writes the set again)
-    tm.begin(SA_K_SEG_WRITE);
-    {
+    // the unsorted set, in SA order, compacted (a round that turns out dense,
+    // or falls back, ignores it: segments() writes the set again)
+    auto gather_u = [&]() {
         const uint32_t wb = (uint32_t)((nw + 1 + kWsBlock - 1) / kWsBlock);
         uint32_t* part = c->hist;   // 2 words per block (<= 2 * 256 * kMaxChunks)
         hipLaunchKernelGGL(k_wscan_reduce, dim3(wb), dim3(kBlock), 0, s, (const uint32_t*)cnt_u, (const uint32_t*)cnt_g,
@@ -811,8 +838,29 @@ static int round1_bucketed(sa_context* c, const uint8_t* d_text, uint64_t n, uin
         hipLaunchKernelGGL(k_u_gather, dim3(g), dim3(kBlock), 0, s, (const uint32_t*)list, (const uint32_t*)c->words,
                            (const uint32_t*)ws, (const uint32_t*)cnt_u, (const uint32_t*)cnt_g, so, c->u_pos[0],
                            c->u_idx[0], c->u_g[0], rm);
+    };
+    // one GPU, round 2 keyed by key1 from the text: the round finished from
+    // the staging by one kernel, its verdict in the read-back below; the set
+    // is compacted only when that gives up (cnt_u is still unscanned then).
+    // Otherwise the set is compacted before the counts are read back (its
+    // launches overlap that round trip).
+    const bool try_r2 = round2 && so.rank && !br_.always_u && !so.tmp_rank && br_.sa_off == 0 &&
+                        !(c->dbg & (SA_DEBUG_NO_KEY1_ROUND | SA_DEBUG_NO_ROUND2_FUSED)) && key1_bits(bp.bs) <= 64;
+    if (try_r2) {
+        tm.round_mark();
+        tm.begin(SA_K_SORT_U);
+        const uint64_t per = (uint64_t)kWaves * kR2Batch;
+        const uint32_t g = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((c->host_words[7] + per - 1) / per, 65536));
+        hipLaunchKernelGGL(k_round2_windows, dim3(g), dim3(kBlock), 0, s, (const uint32_t*)list,
+                           (const uint32_t*)c->words, (const uint32_t*)ws, (const uint32_t*)cnt_u,
+                           (const uint32_t*)so.tmp_pos, (const uint32_t*)so.tmp_idx, (const uint32_t*)so.tmp_g, d_text, n,
+                           (const uint16_t*)c->code, bp.bs, m, d_sa, c->words + kUsFlagWord);
+        tm.end();
+    } else {
+        tm.begin(SA_K_SEG_WRITE);
+        gather_u();
+        tm.end();
     }
-    tm.end();
     SA_HIP(hipGetLastError());
     SA_HIP(hipMemcpyAsync(c->host_words, c->words, 64, hipMemcpyDeviceToHost, s));
     SA_HIP(host_sync(s));
@@ -822,14 +870,33 @@ static int round1_bucketed(sa_context* c, const uint8_t* d_text, uint64_t n, uin
     }
     if (c->host_words[6]) {
         SA_TRACE("  bucketed round 1: local sort flags %u, full sort instead", c->host_words[6]);
+        if (try_r2) tm.round_unmark();
         return SA_OK;
     }
     seg[0] = c->host_words[0];
     seg[1] = c->host_words[1];
     seg[2] = c->host_words[2];
     add_bytes(st, SA_K_LOCAL_SORT, seg[1] * 28);   // unsorted set: rank, member bit, 3 tmp words
-    add_bytes(st, SA_K_SEG_WRITE, 8 * (2 * nw + 2) + seg[1] * 24);
-    if (!br_.always_u && seg[1] > n / kSparseDiv) {
+    const bool sparse = br_.always_u || seg[1] <= n / kSparseDiv;
+    if (try_r2) {
+        add_bytes(st, SA_K_SORT_U, seg[1] * 28);   // 3 tmp words, the key's text words, the SA entry
+        if (!sparse) {
+            tm.round_unmark();   // round 1 goes on (the caller's segments())
+        } else if (c->host_words[kUsFlagWord] == 0) {
+            SA_TRACE("  bucketed round 1: round 2 finished from the staging (%llu members)",
+                     (unsigned long long)seg[1]);
+            *round2 = 2;
+        } else {
+            SA_TRACE("  bucketed round 1: round 2 from the staging gave up, the set compacted");
+            *round2 = 1;
+            tm.begin(SA_K_SEG_WRITE);
+            gather_u();
+            tm.end();
+            SA_HIP(hipGetLastError());
+        }
+    }
+    if (!try_r2 || *round2 == 1) add_bytes(st, SA_K_SEG_WRITE, 8 * (2 * nw + 2) + seg[1] * 24);
+    if (!sparse) {
         // dense ranks follow (segments() over every key1): the same sort
         // again, writing every key1 and nothing of the unsorted set
         SegOut full{};

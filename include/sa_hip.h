@@ -102,6 +102,8 @@ enum sa_kernel_kind {
 #define SA_DEBUG_FAST32_SMALL 0x2000u   /* local sort: the fixed-span 32-bit kernel whenever the key span allows it,
                                            whatever the average bucket size (tests: reaches it below 2^28 suffixes;
                                            windows of several buckets still take the measured-span kernel) */
+#define SA_DEBUG_NO_ROUND2_FUSED 0x4000u /* one GPU: round 2 through the compacted unsorted set and segments(), not
+                                           finished from the local sort's staging by k_round2_windows (A/B runs, tests) */
 
 typedef struct {
     int32_t profile;        /* 1: time every launch with HIP events */
