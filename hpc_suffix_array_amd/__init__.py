@@ -3,10 +3,10 @@ construction behind the C ABI of a-rtemis99/hpc_suffix_array
 (src/common/suffix_array.h) plus a 64-bit extended ABI (include/sa_hip.h).
 """
 from ._native import SAError, build_library, device_count, lib  # noqa: F401
-from .builder import (DeviceBuilder, SuffixArray, build_suffix_array, check_suffix_array,  # noqa: F401
-                      count_patterns, find_patterns, lcp_array, locate_patterns, match_patterns,
-                      matching_statistics)
+from .builder import (DeviceBuilder, SuffixArray, build_suffix_array, bwt, check_suffix_array,  # noqa: F401
+                      count_patterns, find_patterns, inverse_suffix_array, lcp_array, locate_patterns,
+                      match_patterns, matching_statistics)
 
 __all__ = ["SAError", "DeviceBuilder", "SuffixArray", "build_suffix_array", "check_suffix_array",
            "lcp_array", "find_patterns", "count_patterns", "locate_patterns", "match_patterns",
-           "matching_statistics", "build_library", "device_count", "lib"]
+           "matching_statistics", "bwt", "inverse_suffix_array", "build_library", "device_count", "lib"]

@@ -35,6 +35,11 @@ FIND_LANE = 1
 FIND_WAVE = 2
 FIND_LANE_MAX = 3584
 FIND_MODES = {"auto": FIND_AUTO, "lane": FIND_LANE, "wave": FIND_WAVE}
+# sa_bwt statistics (include/sa_hip.h SA_BWT_STATS): uint64 words [0] primary,
+# [1] runs, [2 + c] count of byte c; BWT_TILE: the ranks one workgroup of the
+# BWT kernel handles per iteration (csrc/sa_bwt.h kBwtTile)
+BWT_STATS = 258
+BWT_TILE = 4096
 
 # every symbol include/*.h declares
 DROPIN_SYMBOLS = ["create_suffix_array", "destroy_suffix_array", "build_suffix_array",
@@ -46,6 +51,7 @@ EXT_SYMBOLS = ["sa_context_create", "sa_context_destroy", "sa_context_set_debug"
                "sa_count_below_u64_device", "sa_select_u8_device",
                "sa_find_device", "sa_find", "sa_find_ex",
                "sa_match_device", "sa_matching_stats_device", "sa_match", "sa_matching_stats",
+               "sa_bwt_device", "sa_bwt", "sa_inverse_device", "sa_inverse",
                "sa_dist_begin", "sa_dist_cuts", "sa_dist_plan_cuts", "sa_dist_reserve", "sa_dist_release", "sa_dist_round1", "sa_dist_req_count", "sa_dist_req_fill",
                "sa_dist_answer", "sa_dist_refine",
                "sa_last_error", "sa_host_syncs", "sa_device_count", "sa_version", "sa_struct_size"]
@@ -244,7 +250,15 @@ def lib() -> ctypes.CDLL:
     L.sa_match.restype = i32
     L.sa_matching_stats.argtypes = [vp, u64, vp, i32, vp, u64, u64, vp, vp, vp, ctypes.c_uint32]
     L.sa_matching_stats.restype = i32
-    DI = ctypes.POINTER(SaDistInfo)
+    L.sa_bwt_device.argtypes = [vp, u64, vp, vp, vp, vp]
+    L.sa_bwt_device.restype = i32
+    L.sa_bwt.argtypes = [vp, u64, vp, i32, vp, vp]
+    L.sa_bwt.restype = i32
+    L.sa_inverse_device.argtypes = [vp, u64, vp, vp, vp]
+    L.sa_inverse_device.restype = i32
+    L.sa_inverse.argtypes = [vp, u64, i32, vp]
+    L.sa_inverse.restype = i32
+    DI =ctypes.POINTER(SaDistInfo)
     L.sa_dist_begin.argtypes = [vp, vp, u64, i32, i32, ctypes.POINTER(ctypes.c_uint32), vp, vp, DI]
     L.sa_dist_cuts.argtypes = [vp, ctypes.POINTER(u64), DI]
     L.sa_dist_plan_cuts.argtypes = [i32, u64, i32, ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_uint32),

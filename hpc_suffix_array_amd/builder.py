@@ -270,6 +270,58 @@ def matching_statistics(text, sa, query, max_len: int = 0, mode: str = "auto", b
     return (out[0], out[1], out[2]) if bounds else out[0]
 
 
+def _bwt_host(t_ptr, n: int, sa_ptr, width: int, stats: bool):
+    """sa_bwt over host pointers: (bwt uint8[n], the SA_BWT_STATS words or None)."""
+    out = np.empty(max(n, 1), dtype=np.uint8)
+    st = np.zeros(N.BWT_STATS, dtype=np.uint64) if stats else None
+    N.check(N.lib().sa_bwt(t_ptr if n else None, n, sa_ptr if n else None, width, out.ctypes.data,
+                           st.ctypes.data if stats else None), "sa_bwt")
+    return out[:n], st
+
+
+def bwt(text, sa, stats: bool = False):
+    """Burrows-Wheeler transform of ``text`` from its suffix array ``sa``, on
+    the GPU (sa_bwt).
+
+    ``bwt[r] = text[sa[r] - 1]``, and ``text[n - 1]`` at the primary index,
+    the one rank with ``sa[r] == 0``: n bytes, a permutation of the text's.
+    Returns ``(bwt, primary)``, a uint8 array and an int; with ``stats=True``
+    ``(bwt, primary, runs, counts)``: the number of maximal runs of equal
+    bytes in ``bwt`` and the int64[256] byte histogram, both counted by the
+    same kernel.  Without ``stats`` the kernel does neither and the primary
+    index is looked up in the host ``sa``."""
+    t, s = _text_and_sa(text, sa)
+    N.require_device()
+    n = int(t.size)
+    out, st = _bwt_host(t.ctypes.data, n, s.ctypes.data, 8 if s.dtype == np.int64 else 4, stats)
+    if stats:
+        return out, int(st[0]), int(st[1]), st[2:].astype(np.int64)
+    zero = np.flatnonzero(s == 0)
+    if n and zero.size != 1:
+        raise N.SAError(f"sa_bwt: the SA holds {zero.size} entries equal to 0, not one")
+    return out, int(zero[0]) if n else 0
+
+
+def inverse_suffix_array(sa, width: int = 4):
+    """Inverse of the suffix array ``sa`` on the GPU (sa_inverse):
+    ``isa[sa[r]] = r``, uint32 (width 4) or int64 (width 8).  An ``sa`` that
+    is not a permutation of 0 .. n-1 raises SAError."""
+    if width not in (4, 8):
+        raise ValueError("width must be 4 or 8")
+    s = np.ascontiguousarray(sa)
+    if s.dtype not in (np.uint32, np.int32, np.int64):
+        s = s.astype(np.int64)
+    n = int(s.size)
+    if s.itemsize != width:   # the C entry point takes input and output at one width
+        if width == 4 and n and (int(s.min()) < 0 or int(s.max()) >= n):
+            raise N.SAError("sa_inverse: SA entry out of range")
+        s = s.astype(np.int64 if width == 8 else np.uint32)
+    N.require_device()
+    out = np.empty(max(n, 1), dtype=np.uint32 if width == 4 else np.int64)
+    N.check(N.lib().sa_inverse(s.ctypes.data if n else None, n, width, out.ctypes.data), "sa_inverse")
+    return out[:n]
+
+
 class SuffixArray:
     """The reference's SuffixArray object (suffix_array.h:16-21) driven
     through the drop-in C symbols of libsa_hip.so.
@@ -323,6 +375,15 @@ class SuffixArray:
         c = self.p.contents
         ln, lo, hi = _match_host(c.str, self.n, ctypes.cast(c.sa, ctypes.c_void_p).value, 4, [pattern], mode, True)
         return int(ln[0]), int(lo[0]), int(hi[0])
+
+    def bwt(self) -> tuple:
+        """(bytes, primary): the Burrows-Wheeler transform of the text and its
+        primary index (sa_bwt at width 4 over the object's own str / sa;
+        build() first)."""
+        N.require_device()
+        c = self.p.contents
+        out, st = _bwt_host(c.str, self.n, ctypes.cast(c.sa, ctypes.c_void_p).value, 4, True)
+        return out.tobytes(), int(st[0])
 
     def count(self, pattern) -> int:
         lo, hi = self.find(pattern)
@@ -466,6 +527,24 @@ class DeviceBuilder:
                                                 self._ptr(d_len), None if d_lo is None else self._ptr(d_lo),
                                                 None if d_hi is None else self._ptr(d_hi), N.FIND_MODES[mode], s),
                 "sa_matching_stats_device")
+
+    def bwt(self, d_text, n: int, d_sa, d_bwt, d_stats=None, stream=None) -> None:
+        """Burrows-Wheeler transform of the text from the SA at d_sa into the
+        n bytes at d_bwt (any byte alignment), everything in HBM
+        (sa_bwt_device).  ``d_stats``: N.BWT_STATS uint64 words in device
+        memory ([0] primary index, [1] runs, [2 + c] count of byte c), zeroed
+        and filled by the call; None skips the statistics.  Enqueued on
+        ``stream``; does not wait for it."""
+        s = None if stream is None else ctypes.c_void_p(int(stream))
+        N.check(self.L.sa_bwt_device(self._ptr(d_text), n, self._ptr(d_sa), self._ptr(d_bwt),
+                                     None if d_stats is None else self._ptr(d_stats), s), "sa_bwt_device")
+
+    def inverse(self, n: int, d_sa, d_isa, stream=None) -> None:
+        """Inverse suffix array of the SA at d_sa into the n uint32 at d_isa
+        (16-byte aligned, not d_sa): d_isa[d_sa[r]] = r (sa_inverse_device).
+        Waits for ``stream``; raises SAError when d_sa is not a permutation."""
+        s = None if stream is None else ctypes.c_void_p(int(stream))
+        N.check(self.L.sa_inverse_device(self.ctx, n, self._ptr(d_sa), self._ptr(d_isa), s), "sa_inverse_device")
 
     def close(self) -> None:
         if self.ctx:

@@ -1852,8 +1852,8 @@ static const uint64_t* permute_levels(sa_context* c, const Src& src, uint64_t n,
 // (dest, value) pairs of `src` placed by dest into out[0, n) by the
 // coalesced permutation: LCP's PHI.  Holes (0) and misplaced pairs set bits
 // of *err; *err bit 128: a stripe overflowed (the caller runs it again with
-// stripes = 1).
-template <class Src, int TAG>
+// stripes = 1).  SUB: k_perm_place's (what is written is the value - SUB).
+template <class Src, int TAG, uint32_t SUB = 0>
 static int place_by_permutation(sa_context* c, const Src& src, uint64_t n, uint32_t* out, uint32_t* err,
                                 hipStream_t s, uint32_t stripes) {
     const PermPlan p = plan_check(n, kChkSubA);
@@ -1862,7 +1862,7 @@ static int place_by_permutation(sa_context* c, const Src& src, uint64_t n, uint3
     int rc = SA_OK;
     const uint64_t* placed = permute_levels<Src, 32, TAG>(c, src, n, p, plan_stripes(c, n, p, stripes), err, s, &rc);
     if (rc) return rc;
-    hipLaunchKernelGGL((k_perm_place<kPermBlock, false, TAG>), dim3((uint32_t)((n + (1ull << kPermSub) - 1) >> kPermSub)),
+    hipLaunchKernelGGL((k_perm_place<kPermBlock, false, TAG, SUB>), dim3((uint32_t)((n + (1ull << kPermSub) - 1) >> kPermSub)),
                        dim3(kPermBlock), 0, s, placed, n, out, err);
     SA_HIP(hipGetLastError());
     return SA_OK;
@@ -2185,6 +2185,8 @@ static int global_ctx(uint64_t n, sa_context** out) {
 #include "sa_find.h"
 // longest-match queries and matching statistics over the same search core
 #include "sa_match.h"
+// the Burrows-Wheeler transform and the inverse suffix array of a built SA
+#include "sa_bwt.h"
 
 using namespace sa;
 

@@ -414,7 +414,10 @@ struct NextHist {
 // and added to the global counts once.
 // TAG: 1 for the checker's pass A (sa_check.h), 2 for LCP's PHI (sa_lcp.h),
 // so profiles tell them apart
-template <int BLOCK, bool HIST = false, int TAG = 0>
+// SUB: subtracted from every value as it is written (the hole test and the
+// counts see the value placed): 1 stores the inverse suffix array itself from
+// pass A's r + 1 (sa_bwt.h); 0 everywhere else, where nothing is subtracted
+template <int BLOCK, bool HIST = false, int TAG = 0, uint32_t SUB = 0>
 __global__ __launch_bounds__(BLOCK) void k_perm_place(const uint64_t* __restrict__ in, uint64_t n,
                                                        uint32_t* __restrict__ rank, uint32_t* __restrict__ err,
                                                        NextHist nh = NextHist{}, uint32_t spb = 1) {
@@ -463,7 +466,10 @@ __global__ __launch_bounds__(BLOCK) void k_perm_place(const uint64_t* __restrict
                 v.z = s_r[q + 2];
                 v.w = s_r[q + 3];
                 hole |= (v.x == 0u) | (v.y == 0u) | (v.z == 0u) | (v.w == 0u);
-                *reinterpret_cast<uint4*>(rank + base + q) = v;
+                if constexpr (SUB != 0u)
+                    *reinterpret_cast<uint4*>(rank + base + q) = make_uint4(v.x - SUB, v.y - SUB, v.z - SUB, v.w - SUB);
+                else
+                    *reinterpret_cast<uint4*>(rank + base + q) = v;
                 count(base + q, v.x);
                 count(base + q + 1, v.y);
                 count(base + q + 2, v.z);
@@ -471,7 +477,7 @@ __global__ __launch_bounds__(BLOCK) void k_perm_place(const uint64_t* __restrict
             } else {
                 for (uint32_t i = q; i < valid; ++i) {
                     hole |= s_r[i] == 0u;
-                    rank[base + i] = s_r[i];
+                    rank[base + i] = s_r[i] - SUB;
                     count(base + i, s_r[i]);
                 }
             }

@@ -287,6 +287,57 @@ int sa_matching_stats(const uint8_t* text, uint64_t n, const void* sa, int sa_wi
                       const uint8_t* query, uint64_t m, uint64_t max_len,
                       uint64_t* len_out, uint64_t* lo_out, uint64_t* hi_out, uint32_t flags);
 
+/* ---- Burrows-Wheeler transform and inverse suffix array -----------------
+ * (csrc/sa_bwt.h).  Order: the builder's (unsigned bytes, end of string
+ * smallest).  For a text of n bytes and its suffix array SA:
+ *   bwt[r] = text[SA[r] - 1] where SA[r] > 0, and bwt[r] = text[n - 1] at the
+ *   one rank with SA[r] == 0.  That rank is the primary index (= ISA[0]).  The
+ *   output is n bytes, a permutation of the text's bytes; for a text that ends
+ *   in a unique smallest byte it is the classical BWT of the text's rotations.
+ *   (The (n+1)-row form of text$ is: text[n - 1] first, then these n bytes
+ *   with the primary row replaced by $, primary index + 1: INTEGRATION.md.)
+ *   runs      the number of maximal runs of equal bytes in bwt[0, n): 0 for
+ *             n == 0, 1 for a text of one symbol.
+ *   counts[c] the occurrences of byte c in bwt (= in the text).
+ *   isa[SA[r]] = r.
+ * Statistics are SA_BWT_STATS uint64 words: [0] primary, [1] runs, [2 + c]
+ * the count of byte c. */
+#define SA_BWT_STATS 258
+
+/* d_text: n bytes, d_sa: n uint32, d_bwt: n bytes, d_stats: SA_BWT_STATS
+ * uint64 or NULL, all in device memory; n <= 2^32 - 1.  Asynchronous on
+ * `stream` (no host wait, no context, no workspace).  Checked before any HIP
+ * call: a NULL d_text, d_sa or d_bwt with n > 0, d_bwt == d_text or d_bwt ==
+ * d_sa, and n too large are SA_E_INVALID.  n == 0 is SA_OK without a launch
+ * (d_stats, if given, is zeroed).
+ * d_bwt may have any byte alignment; exactly d_bwt[0, n) is written.  With
+ * d_stats == NULL no histogram or run work is done (another kernel
+ * instantiation); with d_stats every call zeroes the words itself on the
+ * stream, so two calls in a row give the same numbers.
+ * Precondition: d_sa is a valid suffix array of the text.  When it is not,
+ * the bytes and statistics are unspecified, but no load leaves d_text[0, n)
+ * or d_sa[0, n): an entry >= n is clamped, never dereferenced, and the
+ * reported primary lies in [0, n]. */
+int sa_bwt_device(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa, uint8_t* d_bwt,
+                  uint64_t* d_stats /* SA_BWT_STATS words in device memory, or NULL */, void* stream);
+/* Host in, host out: sa has width sa_width (4 or 8; a width-8 entry outside
+ * [0, n) is SA_E_INVALID before any device work).  Allocates, uses and frees
+ * device buffers.  n == 0 is SA_OK without a device, stats_out zeroed. */
+int sa_bwt(const uint8_t* text, uint64_t n, const void* sa, int sa_width, uint8_t* bwt_out,
+           uint64_t* stats_out /* SA_BWT_STATS words, or NULL */);
+
+/* d_isa[d_sa[r]] = r for r < n, by the coalesced permutation of the LCP path
+ * (workspace of ctx).  d_isa: exactly n uint32 in device memory, 16-byte
+ * aligned (the placement stores 16 bytes at a time; nothing past d_isa[n - 1]
+ * is written), not d_sa; a misaligned or aliasing d_isa is SA_E_INVALID.
+ * Synchronises `stream` before returning.  A d_sa that is not a permutation
+ * of [0, n) (a hole, a duplicate, an entry out of range) is SA_E_INVALID,
+ * "not a permutation" in sa_last_error().  n == 0 is SA_OK. */
+int sa_inverse_device(sa_context* ctx, uint64_t n, const uint32_t* d_sa, uint32_t* d_isa, void* stream);
+/* Host in, host out: sa and isa_out have width sa_width (4 or 8; width-8
+ * entries outside [0, n) are SA_E_INVALID before any device work). */
+int sa_inverse(const void* sa, uint64_t n, int sa_width, void* isa_out /* width sa_width */);
+
 /* ---- building blocks of the range-partitioned multi-GPU build ----------
  * (hpc_suffix_array_amd/distributed.py drives these per rank; the exchange
  * steps between them are RCCL collectives over xGMI.)                      */
