@@ -66,7 +66,8 @@ class SAError(RuntimeError):
 DEBUG_FLAGS = {"no_cmp": 0x1, "no_pk8": 0x2, "no_pad": 0x4, "pad_overflow": 0x8, "no_fast32": 0x10,
                "no_pivot": 0x20, "perm_always": 0x40, "no_xq": 0x80, "xq_overflow": 0x100,
                "no_tied": 0x200, "no_key1_round": 0x400, "no_eonly": 0x800,
-               "eonly": 0x1000, "fast32_small": 0x2000, "no_round2_fused": 0x4000}
+               "eonly": 0x1000, "fast32_small": 0x2000, "no_round2_fused": 0x4000,
+               "ls_one_wg": 0x8000}
 
 
 def debug_bits(names) -> int:

@@ -17,7 +17,13 @@
 using namespace sa;
 
 // per-phase clock64() spans of each workgroup's thread 0 (k_bucket_sort's
-// Probe hook), summed into words[32 ..] as 7 u64
+// Probe hook), summed into words[32 ..] as 7 u64.  The marks keep their
+// numbers under SA_LS_HRANK, but the work moved: "load" (ticket, zeroing and
+// their barrier) is empty, "histogram" also stores the indices and issues
+// the first third of the next window's loads, "scatter" places the words
+// without an atomic and issues the second third, "net-sort" ends with the
+// last third.  The two-atomic flow (-DSA_LS_HRANK=0) issues all 18 loads per
+// lane at the end of "scatter": most of that phase is their issue stall.
 struct ClockProbe {
     uint64_t acc[7] = {0, 0, 0, 0, 0, 0, 0}, last = 0;
     __device__ __forceinline__ void mark(int k) {

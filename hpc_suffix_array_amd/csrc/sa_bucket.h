@@ -42,6 +42,8 @@
 //   k_bucket_sort_lsd windows with clustered keys: LSD passes in LDS
 //   k_wscan_* + k_u_gather  the unsorted set in SA order
 #pragma once
+#include <type_traits>
+
 #include "sa_kernels.h"
 
 namespace sa {
@@ -1374,7 +1376,10 @@ __device__ __forceinline__ void sort_sub_lds(uint64_t* __restrict__ s_w, uint32_
 
 // Instrumentation hook of k_bucket_sort: mark(k) at the end of phase k (0
 // load, 1 histogram, 2 scan, 3 scatter, 4 sub-bucket sort, 5 U scan, 6 store;
-// -1 = window start), flush(words) once per workgroup.  The library uses
+// -1 = window start; with SA_LS_HRANK phase 0 is empty -- ticket, zeroing and
+// their barrier are gone -- phase 1 also holds the index stores, phases 1, 3
+// and 4 each the issue of a third of the next window's loads),
+// flush(words) once per workgroup.  The library uses
 // NoProbe (compiled away); microbench_bucket.hip passes a clock64() probe.
 struct NoProbe {
     __device__ __forceinline__ void mark(int) {}
@@ -1823,12 +1828,13 @@ __device__ __forceinline__ void sort_sub_words_lds(uint32_t* __restrict__ s_k, u
 
 // The window's items into registers (slot le = l0 + 64 i; slots past m
 // re-read the last item, see load_raw)
-template <int ITEMS>
+// (I0, I1: items [I0, I1) only -- a window's loads issued in parts)
+template <int ITEMS, int I0 = 0, int I1 = ITEMS>
 __device__ __forceinline__ void load_items(const uint64_t* __restrict__ w_in, uint64_t a, uint32_t m,
                                            uint64_t (&x)[ITEMS]) {
     const uint32_t l0 = slot0<ITEMS>();
 #pragma unroll
-    for (int i = 0; i < ITEMS; ++i) {
+    for (int i = I0; i < I1; ++i) {
         const uint32_t le = l0 + i * kWave;
         x[i] = w_in[a + (le < m ? le : m - 1)];
     }
@@ -1877,12 +1883,12 @@ __device__ __forceinline__ uint32_t xq_offset(const uint32_t* __restrict__ hx, u
 // items past their chunk, inside keys_u's slack, and are masked where the
 // items are used.  The slots are no longer in window order; the sort does not
 // need them to be.
-template <int ITEMS>
+template <int ITEMS, int I0 = 0, int I1 = ITEMS>
 __device__ __forceinline__ void load_items_cr(const uint64_t* __restrict__ w_in, const uint32_t (&rv)[3],
                                               uint64_t (&x)[ITEMS]) {
     const uint32_t lane = lane_id();
 #pragma unroll
-    for (int i = 0; i < ITEMS; ++i) {
+    for (int i = I0; i < I1; ++i) {
         const uint32_t base = (uint32_t)__builtin_amdgcn_readlane((int)rv[0], i);
         x[i] = (w_in + base)[lane];
     }
@@ -1900,14 +1906,14 @@ __device__ __forceinline__ void load_rows_xq(const uint32_t* __restrict__ rows, 
     for (int t = 0; t < 3; ++t) rv[t] = rows[t * ROWS + r];
 }
 
-template <int ITEMS>
+template <int ITEMS, int I0 = 0, int I1 = ITEMS>
 __device__ __forceinline__ void load_items_xq(const uint64_t* __restrict__ w_in, const uint32_t (&rv)[3], uint32_t m,
                                               uint64_t (&x)[ITEMS]) {
     const uint32_t l0 = slot0<ITEMS>();
     const uint32_t lane = lane_id();
     const uint32_t last = m - 1;
 #pragma unroll
-    for (int i = 0; i < ITEMS; ++i) {
+    for (int i = I0; i < I1; ++i) {
         const uint32_t le = l0 + i * kWave;
         const uint32_t lc = le < m ? le : last;
         const uint32_t da = (uint32_t)__builtin_amdgcn_readlane((int)rv[0], i);
@@ -1990,6 +1996,49 @@ __global__ __launch_bounds__(kBlock) void k_window_rows(const uint32_t* __restri
 #ifndef SA_LS_CLAIMS
 #define SA_LS_CLAIMS 1   // (must divide ITEMS; 3 / 6 / 9 at a time measured no faster: profiles/r06_t_ab_local_sort_claims.txt)
 #endif
+// SA_LS_HRANK: the histogram's atomic returns each item's rank inside its
+// sub-bucket, so the scatter needs no second atomic (slot = scanned start +
+// rank); the item's index goes to s_x there too, so the items are dead once
+// their 32 key bits and ranks are kept and the next window's loads can go
+// out anywhere later (SA_LS_HRANK_PF); every thread keeps its five
+// sub-bucket boundaries from the scan in registers and zeroes its counter
+// words at the window's tail, and the next-but-one window's ticket, taken by
+// thread 0 after the histogram, is published by the scatter's barrier: six
+// barriers per window, not seven.  0: the two-atomic flow (histogram, then
+// claims in the scatter).
+#ifndef SA_LS_HRANK
+#define SA_LS_HRANK 1
+#endif
+// SA_LS_HRANK_PF: where the HRANK flow issues the next window's loads, as
+// the number of items whose loads are out by each of five program points:
+// after the histogram, the scan, the scatter, the sub-bucket sorts and the U
+// walk (the two-atomic flow: all after the scatter, its items are live until
+// then).  A burst of 18 loads per lane stalls the wave at issue until the
+// CU's memory pipeline has taken them -- most of what the phase clocks of
+// microbench_bucket.hip show as "scatter" in the two-atomic flow; in parts,
+// between phases that use no global memory, the stall goes away (DESIGN.md
+// section 9, profiles/r09_*).  3: thirds after the histogram, the scatter and
+// the sorts (default); 6: finer parts, measured the same; 1: all after the
+// histogram and 0: all after the scatter, both no faster than the two-atomic
+// flow; 5: thirds from the scatter on
+#ifndef SA_LS_HRANK_PF
+#define SA_LS_HRANK_PF 3
+#endif
+#if SA_LS_HRANK_PF == 0
+#define SA_LS_PF_TABLE {0, 0, 18, 18, 18}
+#elif SA_LS_HRANK_PF == 1
+#define SA_LS_PF_TABLE {18, 18, 18, 18, 18}
+#elif SA_LS_HRANK_PF == 3
+#define SA_LS_PF_TABLE {6, 6, 12, 18, 18}
+#elif SA_LS_HRANK_PF == 5
+#define SA_LS_PF_TABLE {0, 0, 6, 12, 18}
+#elif SA_LS_HRANK_PF == 6
+#define SA_LS_PF_TABLE {3, 6, 9, 15, 18}
+#endif
+constexpr int kLsPfHr[5] = SA_LS_PF_TABLE;
+constexpr int kLsPfOld[5] = {0, 0, 18, 18, 18};
+template <int P>
+using pf_point = std::integral_constant<int, P>;   // k_bucket_sort's prefetch points
 template <int BLOCK, int ITEMS, class Probe = NoProbe, bool XQ = false, int LSV = 0, bool CR = false>
 __global__ __launch_bounds__(BLOCK, 4) void k_bucket_sort(const uint64_t* __restrict__ keys_in,
                                                        const uint4* __restrict__ hdr, uint32_t rb, uint32_t bits,
@@ -2037,11 +2086,17 @@ __global__ __launch_bounds__(BLOCK, 4) void k_bucket_sort(const uint64_t* __rest
         asm("v_lshlrev_b32_e64 %0, %1, 4" : "=v"(r) : "v"(y << 4));
         return r;
     };
+    constexpr bool HR = SA_LS_HRANK != 0;
+    typedef uint16_t __attribute__((may_alias)) half_t;   // one 16-bit half of a counter word
     Probe probe;
     if (threadIdx.x == 0) {
         s_q[0] = atomicAdd(&words[kTicketWord], 1u);
+        if constexpr (HR) s_q[1] = atomicAdd(&words[kTicketWord], 1u);   // the second window
         s_tot[0] = s_tot[1] = s_tot[2] = 0;
     }
+    // HR: every window leaves the counters zeroed for the next one
+    if constexpr (HR)
+        for (int i = threadIdx.x; i < kSubBuckets / 2; i += BLOCK) s_cnt[i] = 0;
     __syncthreads();
     // window numbers and headers are uniform: scalar registers
     uint32_t q = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_q[0]);
@@ -2058,27 +2113,38 @@ __global__ __launch_bounds__(BLOCK, 4) void k_bucket_sort(const uint64_t* __rest
     } else {
         load_items<ITEMS>(keys_in, h.y, h.z, w);
     }
+    // the next window: its number, whether it exists (uniform), its header
+    // (needed at the prefetch point only; past the last window a dummy
+    // one-item window at 0, loaded but never used -- an unconditional load
+    // keeps the current items dead after the scatter, a conditional one kept
+    // them live through the sort) and, XQ, its row words of this wave (past
+    // the last window: the current one's).  HR: known a window ahead -- here
+    // for the second window, then read after each window's scatter barrier
+    uint32_t qn = 0;
+    bool more = false;
+    uint4 hn = make_uint4(0u, 0u, 1u, 0u);
+    uint32_t rwn[3] = {0u, 0u, 0u};
+    auto next_window = [&](uint32_t ticket, uint32_t cur, uint32_t& qx, bool& mx, uint4& hx,
+                           uint32_t (&rx)[3]) __attribute__((always_inline)) {
+        qx = (uint32_t)__builtin_amdgcn_readfirstlane((int)ticket);
+        mx = qx < nwin;
+        hx = make_uint4(0u, 0u, 1u, 0u);
+        if (mx) hx = hdr[qx];
+        if constexpr (XQ) load_rows_xq<ITEMS, ROWS>(xw.rows + (uint64_t)(mx ? qx : cur) * 3 * ROWS, rx);
+    };
+    if constexpr (HR) next_window(s_q[1], q, qn, more, hn, rwn);
     uint32_t par = 0;
     for (;;) {
         probe.mark(-1);
         const uint32_t j = h.x, m = h.z;
         const uint64_t a = h.y;
         const uint64_t mn = (uint64_t)h.w << rb;
-        if (threadIdx.x == 0) s_q[par ^ 1u] = atomicAdd(&words[kTicketWord], 1u);   // the next window
-        for (int i = threadIdx.x; i < kSubBuckets / 2; i += BLOCK) s_cnt[i] = 0;
-        __syncthreads();
-        const uint32_t qn = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_q[par ^ 1u]);
-        const bool more = qn < nwin;   // uniform
-        // the next window's header (needed at the prefetch point only); past
-        // the last window a dummy one-item window at 0, loaded but never
-        // used -- an unconditional load keeps the current items dead after
-        // the scatter (a conditional one kept them live through the sort)
-        uint4 hn = make_uint4(0u, 0u, 1u, 0u);
-        if (more) hn = hdr[qn];
-        // XQ: the next window's row words of this wave (past the last
-        // window: the current one's), for the prefetch
-        uint32_t rwn[3] = {0u, 0u, 0u};
-        if constexpr (XQ) load_rows_xq<ITEMS, ROWS>(xw.rows + (uint64_t)(more ? qn : q) * 3 * ROWS, rwn);
+        if constexpr (!HR) {
+            if (threadIdx.x == 0) s_q[par ^ 1u] = atomicAdd(&words[kTicketWord], 1u);   // the next window
+            for (int i = threadIdx.x; i < kSubBuckets / 2; i += BLOCK) s_cnt[i] = 0;
+            __syncthreads();
+            next_window(s_q[par ^ 1u], q, qn, more, hn, rwn);
+        }
         probe.mark(0);
         const uint32_t l0 = slot0<ITEMS>();
         // 1. sub-bucket histogram (counts < 2^16: no carry between the halves)
@@ -2093,7 +2159,63 @@ __global__ __launch_bounds__(BLOCK, 4) void k_bucket_sort(const uint64_t* __rest
             if constexpr (XQ && CR) return lane < (uint32_t)__builtin_amdgcn_readlane((int)rv[1], i);
             else return l0 + i * kWave < m;
         };
-        if (sfull) {
+        // the next window's loads due at program point P (SA_LS_HRANK_PF),
+        // behind a scheduling barrier: hoisted, they would be a burst again;
+        // REST: all that are still due (a retried window skips the sort)
+        static_assert(ITEMS == 18, "SA_LS_PF_TABLE");
+        auto prefetch_at = [&](auto pc, auto rest) __attribute__((always_inline)) {
+            constexpr int P = decltype(pc)::value;
+            constexpr int A = P ? (HR ? kLsPfHr[P - 1] : kLsPfOld[P - 1]) : 0;
+            constexpr int B = decltype(rest)::value ? ITEMS : (HR ? kLsPfHr[P] : kLsPfOld[P]);
+            if constexpr (A < B) {
+                __builtin_amdgcn_sched_barrier(0);
+                if constexpr (XQ && CR) load_items_cr<ITEMS, A, B>(keys_in, rwn, w);
+                else if constexpr (XQ) load_items_xq<ITEMS, A, B>(keys_in, rwn, hn.z, w);
+                else load_items<ITEMS, A, B>(keys_in, hn.y, hn.z, w);
+            }
+        };
+        constexpr std::false_type part{};
+        constexpr std::true_type rest{};
+        // HR: per item its key bits below ib (sub-bucket and low bits: at most
+        // 32 of them matter) and, four to a register, the bytes counted in
+        // its sub-bucket before it, modulo 256: a window that is sorted here
+        // has sub-buckets of at most kMaxSub = 64 words, 4 * 63 bytes; the
+        // ranks of a retried window are cut short and never used
+        constexpr int RKW = (ITEMS + 3) / 4;
+        uint32_t kk[HR ? ITEMS : 1], rk[HR ? RKW : 1];
+        uint32_t tk = 0;   // HR, thread 0: the ticket of the window after the next
+        static_assert(4 * kMaxSub <= 256, "byte ranks in 8 bits");
+        if constexpr (HR) {
+#pragma unroll
+            for (int r = 0; r < RKW; ++r) rk[r] = 0;
+            auto count1 = [&](int i, uint32_t le) {
+                const uint32_t k = (uint32_t)(w[i] >> ib);
+                const uint32_t y = k >> low_bits;
+                const uint32_t old = atomicAdd(cnt_word(y), half_inc(y));
+                s_x[le] = (uint32_t)(w[i] & imask);
+                kk[i] = k;
+                rk[i / 4] |= __builtin_amdgcn_ubfe(old, y << 4, 8u) << (8 * (i % 4));
+            };
+            if (sfull) {
+#pragma unroll
+                for (int i = 0; i < ITEMS; ++i) count1(i, l0 + i * kWave);
+            } else {
+#pragma unroll
+                for (int i = 0; i < ITEMS; ++i) {
+                    kk[i] = 0;
+                    if (slot_ok(i)) count1(i, l0 + i * kWave);
+                }
+            }
+            // ... the items are dead: the next window's loads may go out from
+            // here on (a scheduling barrier: hoisted above the histogram, they
+            // would hold a second window of registers), behind thread 0's
+            // ticket for the window after it, whose value is first needed
+            // after the scan (loads return in order: waiting for it waits for
+            // no item)
+            __builtin_amdgcn_sched_barrier(0);
+            if (threadIdx.x == 0) tk = atomicAdd(&words[kTicketWord], 1u);
+            prefetch_at(pf_point<0>{}, part);
+        } else if (sfull) {
 #pragma unroll
             for (int i = 0; i < ITEMS; ++i) {
                 const uint32_t y = (uint32_t)(w[i] >> dsh);
@@ -2111,7 +2233,11 @@ __global__ __launch_bounds__(BLOCK, 4) void k_bucket_sort(const uint64_t* __rest
         __syncthreads();
         probe.mark(1);
         // exclusive scan of the counts and their maximum
+        // bw: the word offsets in s_k at which this thread's four sub-buckets
+        // start, and where the last one ends (HR keeps them: the scatter no
+        // longer turns the starts in s_cnt into ends)
         uint32_t big = 0;
+        uint32_t bw[2 * WPT + 1];
         {
             uint32_t c[2 * WPT], sum = 0, cm = 0;
 #pragma unroll
@@ -2146,22 +2272,44 @@ __global__ __launch_bounds__(BLOCK, 4) void k_bucket_sort(const uint64_t* __rest
                 const uint32_t b0 = b, b1 = b + c[2 * x];
                 s_cnt[WPT * dg + x] = b0 | (b1 << 16);
                 b = b1 + c[2 * x + 1];
+                bw[2 * x] = b0 >> 2;
+                bw[2 * x + 1] = b1 >> 2;
             }
+            bw[2 * WPT] = b >> 2;
+            if constexpr (HR)
+                if (threadIdx.x == 0) s_q[0] = tk;   // (read after the scatter's barrier)
         }
+        prefetch_at(pf_point<1>{}, part);
         __syncthreads();
         probe.mark(2);
+        // HR: the window after the next (next_window above)
+        uint32_t qnn = 0;
+        bool moren = false;
+        uint4 hnn = make_uint4(0u, 0u, 1u, 0u);
+        uint32_t rwnn[3] = {0u, 0u, 0u};
         if ((big >> 2) > kMaxSub) {   // uniform: clustered keys -> the measured-span kernel
             // (XQ: k_window_gather copies the retried windows to their SA
             // positions for it; storing the items here made this kernel spill)
             if (threadIdx.x == 0) retry[atomicAdd(&words[kRetryWord], 1u)] = j;
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (XQ && CR) load_items_cr<ITEMS>(keys_in, rwn, w);
-            else if constexpr (XQ) load_items_xq<ITEMS>(keys_in, rwn, hn.z, w);
-            else load_items<ITEMS>(keys_in, hn.y, hn.z, w);
+            if constexpr (HR) {
+                // the counters back to zero: nothing reads the starts
+#pragma unroll
+                for (int x = 0; x < WPT; ++x) s_cnt[WPT * dg + x] = 0;
+            }
+            prefetch_at(pf_point<2>{}, rest);
             __syncthreads();
+            if constexpr (HR) next_window(s_q[0], q, qnn, moren, hnn, rwnn);
         } else {
             // 2. scatter the 32-bit words into sub-buckets (any order inside
             // one); the indices stay by load slot
+            // HR: the word's byte address is its sub-bucket's scanned start
+            // (a 16-bit read) plus its rank; independent reads, no atomic
+            auto place1 = [&](int i, uint32_t le) {
+                const uint32_t k = kk[HR ? i : 0];
+                const uint32_t st = reinterpret_cast<const half_t*>(s_cnt)[(k >> low_bits) & (uint32_t)(kSubBuckets - 1)];
+                const uint32_t at = st + __builtin_amdgcn_ubfe(rk[HR ? i / 4 : 0], 8u * (i % 4), 8u);
+                *reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(s_k) + at) = ((k & lmask) << kSlotBits) | le;
+            };
             auto scatter1 = [&](int i, uint32_t le) {
                 const uint32_t y = (uint32_t)(w[i] >> dsh);
                 const uint32_t old = atomicAdd(cnt_word(y), half_inc(y));
@@ -2170,7 +2318,18 @@ __global__ __launch_bounds__(BLOCK, 4) void k_bucket_sort(const uint64_t* __rest
                     (((uint32_t)(w[i] >> ib) & lmask) << kSlotBits) | le;
                 s_x[le] = (uint32_t)(w[i] & imask);
             };
-            if (sfull) {
+            (void)place1;
+            (void)scatter1;
+            if constexpr (HR) {
+                if (sfull) {
+#pragma unroll
+                    for (int i = 0; i < ITEMS; ++i) place1(i, l0 + i * kWave);
+                } else {
+#pragma unroll
+                    for (int i = 0; i < ITEMS; ++i)
+                        if (slot_ok(i)) place1(i, l0 + i * kWave);
+                }
+            } else if (sfull) {
                 // claims in groups of SA_LS_CLAIMS (> 1: the atomics' round
                 // trips overlap, at more live registers)
 #pragma unroll
@@ -2201,11 +2360,11 @@ __global__ __launch_bounds__(BLOCK, 4) void k_bucket_sort(const uint64_t* __rest
             // ... the window is in LDS: the next window's loads go out now (a
             // scheduling barrier: hoisted above the scatter, they would hold
             // a second window of registers)
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (XQ && CR) load_items_cr<ITEMS>(keys_in, rwn, w);
-            else if constexpr (XQ) load_items_xq<ITEMS>(keys_in, rwn, hn.z, w);
-            else load_items<ITEMS>(keys_in, hn.y, hn.z, w);
+            prefetch_at(pf_point<2>{}, part);
             __syncthreads();
+            // HR: the window after the next, for its prefetch a window from
+            // now (its header and row words arrive during the sort)
+            if constexpr (HR) next_window(s_q[0], q, qnn, moren, hnn, rwnn);
             probe.mark(3);
             // ... then each thread sorts its four consecutive sub-buckets,
             // largest first, with 4 / 8 / 12 / 16-input networks by the
@@ -2213,13 +2372,32 @@ __global__ __launch_bounds__(BLOCK, 4) void k_bucket_sort(const uint64_t* __rest
             uint32_t nu = 0, ng = 0;
             uint32_t umask = 0;   // bit k: sub-bucket sb0 + k holds a group
             const uint32_t sb0 = 2 * WPT * dg;
+            // the words [lo, hi) of s_k of this thread's sub-bucket sb0 + k
+            // (HR: from the scan's registers; s_cnt holds starts, not ends,
+            // and is not read again)
+            auto sub_range = [&](uint32_t k, uint32_t& lo, uint32_t& hi) __attribute__((always_inline)) {
+                if constexpr (HR) {
+                    static_assert(WPT == 2, "four sub-buckets per thread");
+                    // (assignments, not a conditional over bw[..] lvalues: that
+                    // one becomes an indexed read and puts bw in scratch)
+                    lo = bw[3], hi = bw[4];
+                    if (k == 0) lo = bw[0], hi = bw[1];
+                    if (k == 1) lo = bw[1], hi = bw[2];
+                    if (k == 2) lo = bw[2], hi = bw[3];
+                } else {
+                    const uint32_t sb = sb0 + k;
+                    lo = sb ? end_of(sb - 1) : 0u;
+                    hi = end_of(sb);
+                }
+            };
             uint32_t order = 0;
             {
                 uint32_t o[4];
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    const uint32_t sb = sb0 + k;
-                    o[k] = ((end_of(sb) - (sb ? end_of(sb - 1) : 0u)) << 2) | (uint32_t)k;
+                    uint32_t lo, hi;
+                    sub_range((uint32_t)k, lo, hi);
+                    o[k] = ((hi - lo) << 2) | (uint32_t)k;
                 }
                 sort_net32<4>(o);
 #pragma unroll
@@ -2228,7 +2406,9 @@ __global__ __launch_bounds__(BLOCK, 4) void k_bucket_sort(const uint64_t* __rest
 #pragma unroll 1
             for (uint32_t i = 0; i < 4; ++i) {
                 const uint32_t sb = sb0 + ((order >> (2 * i)) & 3u);
-                const uint32_t lo = sb ? end_of(sb - 1) : 0u, hi = end_of(sb), cnt = hi - lo;
+                uint32_t lo, hi;
+                sub_range(sb - sb0, lo, hi);
+                const uint32_t cnt = hi - lo;
                 const bool wide4 = __ballot(cnt > 4u) != 0ull, wide8 = __ballot(cnt > 8u) != 0ull,
                            wide12 = __ballot(cnt > 12u) != 0ull;   // uniform
                 if (cnt == 0) continue;
@@ -2263,6 +2443,7 @@ __global__ __launch_bounds__(BLOCK, 4) void k_bucket_sort(const uint64_t* __rest
                         keys_out[(a + q) >> so.ksh] = mn + (((uint64_t)sb << low_bits) | (s_k[q] >> kSlotBits));
                     });
             }
+            prefetch_at(pf_point<3>{}, part);
             probe.mark(4);
             // 3. U / U-group offsets (one scan of both; heads = m - U + G)
             uint32_t bu, bg, tu_w, tg_w;
@@ -2282,6 +2463,13 @@ __global__ __launch_bounds__(BLOCK, 4) void k_bucket_sort(const uint64_t* __rest
                 bu = (oug & 0xFFFFu) + (iug & 0xFFFFu) - nu;
                 bg = (oug >> 16) + (iug >> 16) - ng;
             }
+            // HR: nothing reads the starts after the scatter's barrier; each
+            // thread zeroes its counter words for the next window's
+            // histogram, which the window's closing barrier precedes
+            if constexpr (HR) {
+#pragma unroll
+                for (int x = 0; x < WPT; ++x) s_cnt[WPT * dg + x] = 0;
+            }
             // LSV bit 1 (no key samples): s_k holds suffix indices except in
             // the sub-buckets with groups, which the U walk converts
             const bool idx_back = (LSV & 2) && !so.samples;   // uniform
@@ -2296,8 +2484,8 @@ __global__ __launch_bounds__(BLOCK, 4) void k_bucket_sort(const uint64_t* __rest
             if (umask && (so.rank || idx_back)) {
                 uint32_t ku = bu, kg = bg;
                 for (uint32_t um = umask; um; um &= um - 1u) {
-                    const uint32_t sb = sb0 + (uint32_t)__builtin_ctz(um);
-                    const uint32_t lo = sb ? end_of(sb - 1) : 0u, hi = end_of(sb);
+                    uint32_t lo, hi;
+                    sub_range((uint32_t)__builtin_ctz(um), lo, hi);
                     uint32_t head = lo, pr = ~0u;
                     for (uint32_t k = lo; k < hi; ++k) {
                         const uint32_t v = s_k[k], r = v >> kSlotBits;
@@ -2321,6 +2509,7 @@ __global__ __launch_bounds__(BLOCK, 4) void k_bucket_sort(const uint64_t* __rest
                     }
                 }
             }
+            prefetch_at(pf_point<4>{}, part);
             probe.mark(5);
             // 4. the SA, coalesced: the index of each sorted word's load slot
             // (the U / G scan's barrier follows every thread's sort; with
@@ -2362,6 +2551,13 @@ __global__ __launch_bounds__(BLOCK, 4) void k_bucket_sort(const uint64_t* __rest
         if constexpr (XQ && CR) {
             rv[0] = rwn[0];
             rv[1] = rwn[1];
+        }
+        if constexpr (HR) {
+            qn = qnn;
+            more = moren;
+            hn = hnn;
+#pragma unroll
+            for (int t = 0; t < 3; ++t) rwn[t] = rwnn[t];
         }
         par ^= 1u;
     }

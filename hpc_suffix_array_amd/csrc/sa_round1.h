@@ -743,6 +743,8 @@ static int round1_bucketed(sa_context* c, const uint8_t* d_text, uint64_t n, uin
             // XQ chunk rows (sa_bucket.h load_items_cr; tune bit 29: the
             // window-order rows with a per-lane chunk select)
             const bool cr = xq && !(((uint32_t)c->tune >> 29) & 1u);
+            // persistent workgroups of the fixed-span kernel (SA_DEBUG_LS_ONE_WG: one takes every window)
+            const uint32_t ls_grid = (c->dbg & SA_DEBUG_LS_ONE_WG) ? 1u : kBsWpc * (uint32_t)c->cus;
             hipLaunchKernelGGL(k_window_split, dim3(gs), dim3(kBlock), 0, s, (const uint32_t*)list, (const uint32_t*)ws,
                                br, c->words, hdr, retry, 1u, (const uint32_t*)xq_pc, (const uint32_t*)xq_pn, nb_tab, hx,
                                cr ? kBsRows : 0u);
@@ -757,9 +759,9 @@ static int round1_bucketed(sa_context* c, const uint8_t* d_text, uint64_t n, uin
                 xw.hx = hx;
                 xw.rows = xrows;
 #define SA_LS_XQ(V, CR)                                                                                          \
-    hipLaunchKernelGGL((k_bucket_sort<kBsBlock, kBsItems, NoProbe, true, V, CR>), dim3(kBsWpc * (uint32_t)c->cus), \
-                       dim3(kBsBlock), 0, s, (const uint64_t*)c->keys_u, (const uint4*)hdr, bp.bs.rb, br.bits1,  \
-                       bp.ib, c->words, c->keys[0], d_sa, retry, o, xw)
+    hipLaunchKernelGGL((k_bucket_sort<kBsBlock, kBsItems, NoProbe, true, V, CR>), dim3(ls_grid), dim3(kBsBlock), 0, \
+                       s, (const uint64_t*)c->keys_u, (const uint4*)hdr, bp.bs.rb, br.bits1, bp.ib, c->words,      \
+                       c->keys[0], d_sa, retry, o, xw)
                 switch (ls_variant(c) | (cr ? 4 : 0)) {
                 case 1: SA_LS_XQ(1, false); break;
                 case 2: SA_LS_XQ(2, false); break;
@@ -779,9 +781,9 @@ static int round1_bucketed(sa_context* c, const uint8_t* d_text, uint64_t n, uin
                                    c->keys[1]);
             } else {
 #define SA_LS(V)                                                                                                 \
-    hipLaunchKernelGGL((k_bucket_sort<kBsBlock, kBsItems, NoProbe, false, V>), dim3(kBsWpc * (uint32_t)c->cus),  \
-                       dim3(kBsBlock), 0, s, (const uint64_t*)c->keys_u, (const uint4*)hdr, bp.bs.rb, br.bits1,  \
-                       bp.ib, c->words, c->keys[0], d_sa, retry, o)
+    hipLaunchKernelGGL((k_bucket_sort<kBsBlock, kBsItems, NoProbe, false, V>), dim3(ls_grid), dim3(kBsBlock), 0, \
+                       s, (const uint64_t*)c->keys_u, (const uint4*)hdr, bp.bs.rb, br.bits1, bp.ib, c->words,   \
+                       c->keys[0], d_sa, retry, o)
                 switch (ls_variant(c)) {
                 case 1: SA_LS(1); break;
                 case 2: SA_LS(2); break;

@@ -104,6 +104,10 @@ enum sa_kernel_kind {
                                            windows of several buckets still take the measured-span kernel) */
 #define SA_DEBUG_NO_ROUND2_FUSED 0x4000u /* one GPU: round 2 through the compacted unsorted set and segments(), not
                                            finished from the local sort's staging by k_round2_windows (A/B runs, tests) */
+#define SA_DEBUG_LS_ONE_WG 0x8000u      /* local sort: the fixed-span 32-bit kernel launched with one workgroup, so
+                                           every listed window passes through it in ticket order (tests of the
+                                           window-to-window hand-over at sizes an oracle sorts; phase times of one
+                                           workgroup); the plan, the windows and the statistics stay the same */
 
 typedef struct {
     int32_t profile;        /* 1: time every launch with HIP events */
