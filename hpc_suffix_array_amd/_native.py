@@ -40,6 +40,14 @@ FIND_MODES = {"auto": FIND_AUTO, "lane": FIND_LANE, "wave": FIND_WAVE}
 # BWT kernel handles per iteration (csrc/sa_bwt.h kBwtTile)
 BWT_STATS = 258
 BWT_TILE = 4096
+# sa_locate flags (include/sa_hip.h SA_LOCATE_*) and the tile of the locate
+# kernel: output slots per tile = the largest query sorted in LDS (csrc/
+# sa_locate.h kLocateTile); LOCATE_SMALL_CHUNKS cuts the large class's radix
+# sort into chunks of 2^14 hits (tests)
+LOCATE_SA_ORDER = 1
+LOCATE_SMALL_CHUNKS = 2
+LOCATE_TILE = 2048
+LOCATE_ORDERS = {"text": 0, "sa": LOCATE_SA_ORDER}
 
 # every symbol include/*.h declares
 DROPIN_SYMBOLS = ["create_suffix_array", "destroy_suffix_array", "build_suffix_array",
@@ -52,6 +60,7 @@ EXT_SYMBOLS = ["sa_context_create", "sa_context_destroy", "sa_context_set_debug"
                "sa_find_device", "sa_find", "sa_find_ex",
                "sa_match_device", "sa_matching_stats_device", "sa_match", "sa_matching_stats",
                "sa_bwt_device", "sa_bwt", "sa_inverse_device", "sa_inverse",
+               "sa_locate_device", "sa_locate",
                "sa_dist_begin", "sa_dist_cuts", "sa_dist_plan_cuts", "sa_dist_reserve", "sa_dist_release", "sa_dist_round1", "sa_dist_req_count", "sa_dist_req_fill",
                "sa_dist_answer", "sa_dist_refine",
                "sa_last_error", "sa_host_syncs", "sa_device_count", "sa_version", "sa_struct_size"]
@@ -259,6 +268,10 @@ def lib() -> ctypes.CDLL:
     L.sa_inverse_device.restype = i32
     L.sa_inverse.argtypes = [vp, u64, i32, vp]
     L.sa_inverse.restype = i32
+    L.sa_locate_device.argtypes = [vp, u64, vp, vp, vp, u64, u64, ctypes.c_uint32, vp, vp, u64, ctypes.POINTER(u64), vp]
+    L.sa_locate_device.restype = i32
+    L.sa_locate.argtypes = [vp, u64, i32, vp, vp, u64, u64, ctypes.c_uint32, vp, vp, u64]
+    L.sa_locate.restype = i32
     DI =ctypes.POINTER(SaDistInfo)
     L.sa_dist_begin.argtypes = [vp, vp, u64, i32, i32, ctypes.POINTER(ctypes.c_uint32), vp, vp, DI]
     L.sa_dist_cuts.argtypes = [vp, ctypes.POINTER(u64), DI]

@@ -207,6 +207,55 @@ def locate_patterns(text, sa, patterns, mode: str = "auto") -> list:
     return [np.sort(s[a:b].astype(np.int64)) for a, b in zip(lo.tolist(), hi.tolist())]
 
 
+def _locate_flags(order: str, chunks: bool = False) -> int:
+    if order not in N.LOCATE_ORDERS:
+        raise ValueError(f"order {order!r}: one of {sorted(N.LOCATE_ORDERS)}")
+    return N.LOCATE_ORDERS[order] | (N.LOCATE_SMALL_CHUNKS if chunks else 0)
+
+
+def locate_intervals(sa, lo, hi, max_hits: int = 0, order: str = "text", _chunks: bool = False):
+    """Text positions of a batch of SA intervals, expanded and sorted on the
+    GPU (sa_locate), in CSR form.
+
+    ``lo`` / ``hi``: what find_patterns or match_patterns return.  Returns
+    ``(offsets, positions)``, both int64: query q has the
+    ``min(hi[q] - lo[q], max_hits)`` positions
+    ``positions[offsets[q]:offsets[q + 1]]`` (``max_hits=0``: no cap), the
+    entries ``sa[lo[q]:lo[q] + count]`` sorted ascending, or as they lie in
+    the SA with ``order="sa"``.  A capped query keeps its first ``max_hits``
+    hits in SA order (then sorted): not the smallest positions."""
+    flags = _locate_flags(order, _chunks)
+    if max_hits < 0:
+        raise ValueError("max_hits is negative")
+    s = np.ascontiguousarray(sa)
+    if s.dtype not in (np.uint32, np.int32, np.int64):
+        s = s.astype(np.int64)
+    lo = np.ascontiguousarray(lo, dtype=np.uint64).reshape(-1)
+    hi = np.ascontiguousarray(hi, dtype=np.uint64).reshape(-1)
+    if lo.size != hi.size:
+        raise ValueError(f"{lo.size} lower and {hi.size} upper bounds")
+    N.require_device()
+    n, nq, width = int(s.size), int(lo.size), 8 if s.dtype == np.int64 else 4
+    cnt = np.where(hi >= lo, hi - lo, 0)          # the C side rejects lo > hi
+    if max_hits:
+        cnt = np.minimum(cnt, np.uint64(max_hits))
+    total = int(cnt.sum(dtype=np.uint64))
+    off = np.zeros(nq + 1, dtype=np.uint64)
+    pos = np.empty(max(total, 1), dtype=np.int64 if width == 8 else np.uint32)
+    N.check(N.lib().sa_locate(s.ctypes.data if n else None, n, width, lo.ctypes.data if nq else None,
+                              hi.ctypes.data if nq else None, nq, int(max_hits), flags, off.ctypes.data,
+                              pos.ctypes.data, total), "sa_locate")
+    return off.astype(np.int64), pos[:total].astype(np.int64)
+
+
+def locate_batch(text, sa, patterns, max_hits: int = 0, order: str = "text", mode: str = "auto"):
+    """find_patterns followed by locate_intervals: ``(offsets, positions)``,
+    the occurrences of pattern q are ``positions[offsets[q]:offsets[q + 1]]``
+    (ascending; ``order="sa"``: SA order; at most ``max_hits`` of them)."""
+    lo, hi = find_patterns(text, sa, patterns, mode)
+    return locate_intervals(sa, lo, hi, max_hits, order)
+
+
 def _match_host(t_ptr, n: int, sa_ptr, width: int, patterns, mode: str, bounds: bool):
     """sa_match over host pointers: (length, lo, hi) as int64 arrays, or the
     lengths alone."""
@@ -545,6 +594,22 @@ class DeviceBuilder:
         Waits for ``stream``; raises SAError when d_sa is not a permutation."""
         s = None if stream is None else ctypes.c_void_p(int(stream))
         N.check(self.L.sa_inverse_device(self.ctx, n, self._ptr(d_sa), self._ptr(d_isa), s), "sa_inverse_device")
+
+    def locate(self, n: int, d_sa, d_lo, d_hi, nq: int, d_off, d_pos, pos_cap: int, max_hits: int = 0,
+               order: str = "text", stream=None, _chunks: bool = False) -> int:
+        """Sorted hit lists of nq SA intervals in CSR form, everything in HBM
+        (sa_locate_device): d_lo / d_hi (uint32) as find writes them, d_off
+        nq + 1 uint64, d_pos pos_cap uint32 at any 4-byte alignment.  Returns
+        the total number of hits.  Positions are written only when the total
+        fits pos_cap and d_pos is not None: call once with ``d_pos=None`` to
+        size the output, allocate, and call again.  Waits for ``stream``."""
+        s = None if stream is None else ctypes.c_void_p(int(stream))
+        total = ctypes.c_uint64()
+        N.check(self.L.sa_locate_device(self.ctx, n, self._ptr(d_sa), self._ptr(d_lo), self._ptr(d_hi), nq,
+                                        int(max_hits), _locate_flags(order, _chunks), self._ptr(d_off),
+                                        None if d_pos is None else self._ptr(d_pos), int(pos_cap),
+                                        ctypes.byref(total), s), "sa_locate_device")
+        return int(total.value)
 
     def close(self) -> None:
         if self.ctx:

@@ -2623,6 +2623,10 @@ static int scan_i64(int64_t* d_v, uint64_t m, hipStream_t s) {
     return SA_OK;
 }
 
+// batched locate over a built SA: sorted hit lists in CSR form (its offsets
+// are summed by scan_i64 above)
+#include "sa_locate.h"
+
 extern "C" {
 
 int sa_running_max_i64_device(int64_t* d_v, uint64_t m, void* stream) {

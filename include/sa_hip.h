@@ -342,6 +342,54 @@ int sa_inverse_device(sa_context* ctx, uint64_t n, const uint32_t* d_sa, uint32_
  * entries outside [0, n) are SA_E_INVALID before any device work). */
 int sa_inverse(const void* sa, uint64_t n, int sa_width, void* isa_out /* width sa_width */);
 
+/* ---- batched locate: sorted hit lists in CSR form ------------------------
+ * (csrc/sa_locate.h).  Inputs are a suffix array of n entries and nq SA
+ * intervals [lo[q], hi[q]) -- what sa_find or sa_match return.  With
+ *   c[q] = min(hi[q] - lo[q], max_hits)      (max_hits == 0: no cap)
+ * the output is off[0] = 0, off[q + 1] = off[q] + c[q] (nq + 1 uint64; the
+ * total is off[nq]) and pos[off[q] .. off[q + 1]) = SA[lo[q] .. lo[q] + c[q]),
+ * sorted ascending.  A capped query therefore returns the FIRST max_hits hits
+ * IN SA ORDER, then sorted: deterministic, but not the max_hits smallest
+ * positions.  With SA_LOCATE_SA_ORDER the sort is skipped and the slices are
+ * concatenated as they lie in the SA.  The text is never read.  Queries may
+ * overlap or repeat, so the total may exceed n: offsets and every index into
+ * pos are 64-bit.
+ * A query with c[q] <= SA_LOCATE_TILE is sorted in LDS together with the
+ * other queries of its output tile; a longer one goes through the context's
+ * radix sort.  The class is decided on the capped count. */
+#define SA_LOCATE_SA_ORDER 1u      /* positions in SA order, not sorted */
+#define SA_LOCATE_SMALL_CHUNKS 2u  /* tests: the large class sorted in chunks of 2^14 hits (production: 2^28) */
+#define SA_LOCATE_TILE 2048        /* output slots per tile = the largest query of the small class */
+
+/* d_sa: n uint32, d_lo / d_hi: nq uint32, d_off: nq + 1 uint64, d_pos: pos_cap
+ * uint32 or NULL, all in device memory; n and nq <= 2^32 - 1.
+ * Always fills d_off and *total.  Positions are written only when d_pos is
+ * not NULL and *total <= pos_cap; otherwise the call returns SA_OK with
+ * *total set and touches nothing in d_pos: the sizing call, after which the
+ * caller allocates and calls again.  Exactly d_pos[0, total) and d_off[0, nq]
+ * are written; d_pos may have any 4-byte alignment (a view such as pos + 1).
+ * Synchronises `stream`: one host wait per call when no query is large (or
+ * nothing is written); with large queries one more per chunk of 2^28 large
+ * hits (the radix sort's own), one when there are several chunks, and one at
+ * the end.  Temporaries are stream-ordered allocations (SA_E_NOMEM when one
+ * fails); the radix sort grows the context's workspace to the chunk.
+ * Checked before any HIP call (SA_E_INVALID): a NULL ctx, d_sa, d_lo, d_hi,
+ * d_off or total, n or nq too large, d_pos == d_sa, unknown flags.  nq == 0
+ * gives off[0] = 0 and total 0 without a launch.
+ * Precondition: lo <= hi <= n.  An interval that breaks it counts as empty,
+ * and no load leaves d_sa[0, n), d_lo[0, nq) or d_hi[0, nq) whatever those
+ * arrays hold. */
+int sa_locate_device(sa_context* ctx, uint64_t n, const uint32_t* d_sa, const uint32_t* d_lo, const uint32_t* d_hi,
+                     uint64_t nq, uint64_t max_hits, uint32_t flags, uint64_t* d_off /* nq + 1 */,
+                     uint32_t* d_pos /* may be NULL */, uint64_t pos_cap, uint64_t* total, void* stream);
+/* Host in, host out: sa and pos_out have width sa_width (4 or 8).  The host
+ * knows the intervals, so it fills off_out and checks before any device work
+ * (SA_E_INVALID): an interval with lo > hi or hi > n, pos_cap below the total,
+ * a width other than 4 or 8, a width-8 SA entry outside [0, n).  nq == 0 or a
+ * total of 0 returns SA_OK without a device. */
+int sa_locate(const void* sa, uint64_t n, int sa_width, const uint64_t* lo, const uint64_t* hi, uint64_t nq,
+              uint64_t max_hits, uint32_t flags, uint64_t* off_out /* nq + 1 */, void* pos_out, uint64_t pos_cap);
+
 /* ---- building blocks of the range-partitioned multi-GPU build ----------
  * (hpc_suffix_array_amd/distributed.py drives these per rank; the exchange
  * steps between them are RCCL collectives over xGMI.)                      */
