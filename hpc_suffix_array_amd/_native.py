@@ -76,7 +76,7 @@ DEBUG_FLAGS = {"no_cmp": 0x1, "no_pk8": 0x2, "no_pad": 0x4, "pad_overflow": 0x8,
                "no_pivot": 0x20, "perm_always": 0x40, "no_xq": 0x80, "xq_overflow": 0x100,
                "no_tied": 0x200, "no_key1_round": 0x400, "no_eonly": 0x800,
                "eonly": 0x1000, "fast32_small": 0x2000, "no_round2_fused": 0x4000,
-               "ls_one_wg": 0x8000}
+               "ls_one_wg": 0x8000, "no_alpha_sample": 0x10000, "alpha_sample_small": 0x20000}
 
 
 def debug_bits(names) -> int:
@@ -120,6 +120,7 @@ class SaStats(ctypes.Structure):
         ("round1_layout", ctypes.c_int32),
         ("round_bytes", ctypes.c_uint64 * SA_MAX_ROUNDS),
         ("round1_windows", ctypes.c_int32 * 4),
+        ("alphabet", ctypes.c_int32),
     ]
 
     def to_dict(self) -> dict:
@@ -149,6 +150,9 @@ class SaStats(ctypes.Structure):
             # bucketed round 1: non-empty windows, one-bucket windows of the fixed-span kernel, windows
             # sorted again with the measured span, skewed windows (first local-sort launch)
             "round1_windows": [int(x) for x in self.round1_windows],
+            # where the dense codes came from: a pass over the text, a sample the first bucket pass
+            # proved, or a sample it refuted (the build then ran again with the exact alphabet)
+            "alphabet": {0: "exact", 1: "sampled", 2: "refuted"}.get(self.alphabet, "exact"),
             "kernels": {k: {"ms": self.kern_ms[i], "launches": int(self.kern_launches[i]),
                             "bytes": int(self.kern_bytes[i])} for i, k in enumerate(KERNEL_KINDS)},
         }

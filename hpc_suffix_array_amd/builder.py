@@ -66,7 +66,14 @@ def build_suffix_array(text, width: int = 4, profile: bool = False, return_stats
     n suffixes, round for round as manber_myers.c:94-125).  ``round1``
     (packed): "auto", "lsd" (full radix sort of the packed first key) or
     "bucketed" (two bucket passes + per-window LDS sort).  ``debug`` /
-    ``span_extra`` / ``tune``: forced alternative paths (tests, A/B runs)."""
+    ``span_extra`` / ``tune``: forced alternative paths (tests, A/B runs).
+
+    From 2^26 bytes the packed schedule takes the alphabet from a sample of
+    the text, and the first bucket pass proves it on every byte
+    (``stats["alphabet"]``: "exact", "sampled" or "refuted").  A text with a
+    symbol in none of the sampled blocks pays one wasted first and second
+    pass before the build runs again with the exact alphabet;
+    ``debug=("no_alpha_sample",)`` always scans the whole text instead."""
     t = _as_bytes_array(text)
     n = int(t.size)
     N.require_device()

@@ -185,6 +185,10 @@ struct sa_context {
     int32_t span_extra = 0;
     int32_t tune = 0;
     bool dna = false;   // the text's alphabet is exactly {A, C, G, T} (k_split_text<.., DNA>)
+    // the codes come from a sample of the text (build_packed): the first bucket
+    // pass proves them, and round1_bucketed reports a refuted sample here
+    bool alpha_prove = false;
+    bool alpha_refuted = false;
     bool samples_pending = false;   // round 1 wrote no key1 samples (SegOut::samples = 0)
 };
 
@@ -1419,79 +1423,134 @@ static int build_packed(sa_context* c, const uint8_t* d_text, uint64_t n, uint32
     rc = ensure_u_capacity(c, n);
     if (rc) return rc;
     tm.round_mark();
-    // alphabet -> dense codes (host reads the 256-bit presence mask)
     uint32_t* h_alpha = c->host_words + 64;
     uint16_t* h_code = reinterpret_cast<uint16_t*>(c->host_words + 320);
-    SA_HIP(hipMemsetAsync(c->alpha, 0, 8 * 4, s));
-    tm.begin(SA_K_ALPHABET);
-    {
-        const uint32_t grid = (uint32_t)std::min<uint64_t>((n + kBlock * 16 - 1) / (kBlock * 16), SA_ALPHA_GRID);
-        hipLaunchKernelGGL(k_alphabet, dim3(grid), dim3(kBlock), 0, s, d_text, n, c->alpha);
-    }
-    tm.end();
-    SA_HIP(hipGetLastError());
-    add_bytes(st, SA_K_ALPHABET, n);
-    SA_HIP(hipMemcpyAsync(h_alpha, c->alpha, 8 * 4, hipMemcpyDeviceToHost, s));
     // the text's last bytes: the compact key layout's check (short_suffix_ties)
     const uint32_t tail_n = (uint32_t)std::min<uint64_t>(n, (uint64_t)kMaxK);
     uint8_t* h_tail = reinterpret_cast<uint8_t*>(c->host_words + 2048);
-    SA_HIP(hipMemcpyAsync(h_tail, d_text + (n - tail_n), tail_n, hipMemcpyDeviceToHost, s));
-    SA_HIP(host_sync(s));
-    uint32_t sigma = 0;
-    for (int b = 0; b < 256; ++b) h_code[b] = ((h_alpha[b >> 5] >> (b & 31)) & 1u) ? (uint16_t)(++sigma) : 0;
-    SA_HIP(hipMemcpyAsync(c->code, h_code, 256 * 2, hipMemcpyHostToDevice, s));
-    c->dna = sigma == 4 && h_code['A'] && h_code['C'] && h_code['G'] && h_code['T'];
-    uint32_t K = choose_chars(sigma, n, opts ? opts->init_chars : 0);
-    const uint64_t base = (uint64_t)sigma + 1;
-    const Chunking ch = plan_chunks(n);
-    uint64_t* keys1 = nullptr;
-    uint32_t ksh1 = 0;   // bucketed round 1: keys1 holds every 2^ksh1-th sorted key1
-    c->samples_pending = false;
-    uint32_t P = 0;
-
-    // round 1: sort every suffix by its first K symbols -- bucketed (two
-    // global passes + per-window LDS sort) when the text allows it, else the
-    // LSD sort of the packed key
+    uint32_t sigma = 0, K = 0, Kb = 0;
     BucketPlan bp;
     const int r1 = opts ? opts->round1 : SA_ROUND1_AUTO;
-    // the bucketed round sorts by min_chars symbols (an explicit K as given):
-    // rounding K up to fill radix passes only serves the LSD round, and a
-    // shorter key1 keeps its low bits narrow enough for the fixed-span local
-    // sort and the per-XCD second pass (1 GiB alnum: K 8 -> 7, 16.05 -> 13.59
-    // ms, profiles/r06_h_bench_alnum_k*.log; DNA, ascii127, byte256: the same K)
-    const uint32_t Kb = (opts && opts->init_chars > 0) || sigma <= 1 ? K : min_chars(sigma, n);
-    bool bucketed = plan_bucketed(sigma, n, Kb, r1, c->radix, &bp, 1, (c->dbg & SA_DEBUG_NO_CMP) ? 0 : 1);
-    if (bucketed && bp.bs.cmp && short_suffix_ties(h_tail, n, tail_n, h_code, sigma, bp.bs.s, bp.bs.R))
-        bucketed = plan_bucketed(sigma, n, Kb, r1, c->radix, &bp, 1, 0);
-    // a non-power-of-two alphabet one bit short of packed first-pass items
-    // (1 GiB alnum / ascii127: 65 bits) takes the E-only layout when the
-    // text's last K suffixes pad apart (BucketSpec, sa_kernels.h)
-    const bool force_eonly = (c->dbg & SA_DEBUG_EONLY) != 0;
-    if (bucketed && bp.bs.cmp == 1 && ((sigma & (sigma - 1)) != 0 || force_eonly) && !(c->dbg & SA_DEBUG_NO_EONLY)) {
-        const uint32_t hb = bp.bs.bb - kLoBits;
-        BucketPlan b2;
-        if ((force_eonly || !plan_pk8(bp, hb, c->dbg, true)) && plan_bucketed(sigma, n, Kb, r1, c->radix, &b2, 1, 2) &&
-            (force_eonly || plan_pk8(b2, hb, c->dbg, true)) &&
-            !short_suffix_ties(h_tail, n, tail_n, h_code, sigma, b2.bs.s, b2.bs.R, b2.K))
-            bp = b2;
-    }
+    bool bucketed = false;
+    // alphabet -> dense codes (host reads the 256-bit presence mask) -> the
+    // plan of round 1.  sampled: the mask of a sample of the text
+    // (sa_alpha.h) instead of a pass over all of it; *complete = false when
+    // the text's tail holds a byte the sample missed.
+    auto plan_round1 = [&](bool sampled, bool* complete) -> int {
+        SA_HIP(hipMemsetAsync(c->alpha, 0, 8 * 4, s));
+        tm.begin(SA_K_ALPHABET);
+        if (sampled) {
+            const bool first4k = (c->dbg & SA_DEBUG_ALPHA_SAMPLE_SMALL) != 0;
+            const uint64_t nb = alpha_text_blocks(n), ns = alpha_sample_blocks(n, first4k);
+            hipLaunchKernelGGL(k_alphabet_sample, dim3((uint32_t)std::min<uint64_t>(ns, 2ull * (uint32_t)c->cus)),
+                               dim3(kBlock), 0, s, d_text, n, nb, ns, c->alpha);
+            add_bytes(st, SA_K_ALPHABET, alpha_sample_bytes(n, first4k));
+        } else {
+            const uint32_t grid = (uint32_t)std::min<uint64_t>((n + kBlock * 16 - 1) / (kBlock * 16), SA_ALPHA_GRID);
+            hipLaunchKernelGGL(k_alphabet, dim3(grid), dim3(kBlock), 0, s, d_text, n, c->alpha);
+            add_bytes(st, SA_K_ALPHABET, n);
+        }
+        tm.end();
+        SA_HIP(hipGetLastError());
+        SA_HIP(hipMemcpyAsync(h_alpha, c->alpha, 8 * 4, hipMemcpyDeviceToHost, s));
+        SA_HIP(hipMemcpyAsync(h_tail, d_text + (n - tail_n), tail_n, hipMemcpyDeviceToHost, s));
+        SA_HIP(host_sync(s));
+        // the tail's bytes belong to the mask; one the sample missed shows
+        // before any pass that the sample is not the alphabet
+        *complete = true;
+        for (uint32_t t = 0; t < tail_n; ++t) {
+            const uint32_t x = h_tail[t];
+            if (!((h_alpha[x >> 5] >> (x & 31)) & 1u)) *complete = false;
+            h_alpha[x >> 5] |= 1u << (x & 31);
+        }
+        sigma = 0;
+        for (int b = 0; b < 256; ++b) h_code[b] = ((h_alpha[b >> 5] >> (b & 31)) & 1u) ? (uint16_t)(++sigma) : 0;
+        SA_HIP(hipMemcpyAsync(c->code, h_code, 256 * 2, hipMemcpyHostToDevice, s));
+        c->dna = sigma == 4 && h_code['A'] && h_code['C'] && h_code['G'] && h_code['T'];
+        K = choose_chars(sigma, n, opts ? opts->init_chars : 0);
+        // round 1: sort every suffix by its first K symbols -- bucketed (two
+        // global passes + per-window LDS sort) when the text allows it, else the
+        // LSD sort of the packed key
+        // the bucketed round sorts by min_chars symbols (an explicit K as given):
+        // rounding K up to fill radix passes only serves the LSD round, and a
+        // shorter key1 keeps its low bits narrow enough for the fixed-span local
+        // sort and the per-XCD second pass (1 GiB alnum: K 8 -> 7, 16.05 -> 13.59
+        // ms, profiles/r06_h_bench_alnum_k*.log; DNA, ascii127, byte256: the same K)
+        Kb = (opts && opts->init_chars > 0) || sigma <= 1 ? K : min_chars(sigma, n);
+        bucketed = plan_bucketed(sigma, n, Kb, r1, c->radix, &bp, 1, (c->dbg & SA_DEBUG_NO_CMP) ? 0 : 1);
+        if (bucketed && bp.bs.cmp && short_suffix_ties(h_tail, n, tail_n, h_code, sigma, bp.bs.s, bp.bs.R))
+            bucketed = plan_bucketed(sigma, n, Kb, r1, c->radix, &bp, 1, 0);
+        // a non-power-of-two alphabet one bit short of packed first-pass items
+        // (1 GiB alnum / ascii127: 65 bits) takes the E-only layout when the
+        // text's last K suffixes pad apart (BucketSpec, sa_kernels.h)
+        const bool force_eonly = (c->dbg & SA_DEBUG_EONLY) != 0;
+        if (bucketed && bp.bs.cmp == 1 && ((sigma & (sigma - 1)) != 0 || force_eonly) &&
+            !(c->dbg & SA_DEBUG_NO_EONLY)) {
+            const uint32_t hb = bp.bs.bb - kLoBits;
+            BucketPlan b2;
+            if ((force_eonly || !plan_pk8(bp, hb, c->dbg, true)) && plan_bucketed(sigma, n, Kb, r1, c->radix, &b2, 1, 2) &&
+                (force_eonly || plan_pk8(b2, hb, c->dbg, true)) &&
+                !short_suffix_ties(h_tail, n, tail_n, h_code, sigma, b2.bs.s, b2.bs.R, b2.K))
+                bp = b2;
+        }
+        return SA_OK;
+    };
+    // The alphabet from a sample (n >= kPadMinN; SA_DEBUG_ALPHA_SAMPLE_SMALL:
+    // any n), kept only when round 1 is then the bucketed one: its first pass
+    // stages every byte of the text and proves the sample (k_split_text,
+    // alpha_bad).  Every other plan (sigma <= 1, no bucket layout, a forced
+    // LSD round) takes the exact pass right here, having paid the sample and
+    // one more host round trip.  A sample the first pass refutes -- a symbol
+    // in none of the sampled blocks -- costs that pass and the second, and the
+    // build starts again with the exact alphabet, once.
+    bool sampled = !(c->dbg & SA_DEBUG_NO_ALPHA_SAMPLE) &&
+                   (n >= kPadMinN || (c->dbg & SA_DEBUG_ALPHA_SAMPLE_SMALL)) && c->radix == 0 && r1 != SA_ROUND1_LSD;
+    bool refuted = false;
+    uint64_t* keys1 = nullptr;
+    uint32_t ksh1 = 0;   // bucketed round 1: keys1 holds every 2^ksh1-th sorted key1
+    uint32_t P = 0;
     bool fused = false;
     bool r1_pivot = false;   // round 1 by the pivot split (pivot_round1)
     uint64_t D = 0, m = 0, G = 0;
     uint64_t seg1[3] = {0, 0, 0};
     int r2 = 0;   // round 2 from the local sort's staging (round1_bucketed): 1 gave up, 2 finished the build
-    if (bucketed) {
+    for (;;) {
+        bool complete = true;
+        rc = plan_round1(sampled, &complete);
+        if (rc) return rc;
+        if (sampled && !(bucketed && complete)) {
+            SA_TRACE("packed: sampled alphabet (sigma=%u) not kept: %s", sigma,
+                     complete ? "round 1 is not bucketed" : "the tail holds another symbol");
+            sampled = false;
+            continue;
+        }
+        c->samples_pending = false;
+        if (!bucketed) break;
         bool done = false;
+        // (all 256 values in the sample: nothing left to prove)
+        c->alpha_prove = sampled && sigma < 256;
+        c->alpha_refuted = false;
         rc = round1_bucketed(c, d_text, n, d_sa, bp, full_range(bp, n), s, tm, st, &done, &fused, seg1, &ksh1, true,
                              true, &r2);
+        c->alpha_prove = false;
         if (rc) return rc;
+        if (c->alpha_refuted) {
+            SA_TRACE("packed: the first pass met a symbol outside the sampled alphabet, again with the exact one");
+            sampled = false;
+            refuted = true;
+            continue;
+        }
         bucketed = done;
         if (done) {
             keys1 = c->keys[0];
             P = 2;
             K = bp.K;
         }
+        break;
     }
+    if (st) st->alphabet = refuted ? SA_ALPHABET_REFUTED : sampled ? SA_ALPHABET_SAMPLED : SA_ALPHABET_EXACT;
+    const uint64_t base = (uint64_t)sigma + 1;
+    const Chunking ch = plan_chunks(n);
     if (!bucketed) {
         const uint32_t bits1 = key_bits(base, K);
         SA_TRACE("packed: sigma=%u K=%u bits=%u", sigma, K, bits1);

@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sa_alpha.h"
 #include "sa_search.h"
 
 namespace sa {
@@ -818,6 +819,29 @@ __global__ __launch_bounds__(kBlock) void k_rerank(const uint64_t* __restrict__ 
 }
 
 
+// The lanes' private masks m (k_alphabet's s_m rows) OR-ed into present:
+// one global atomic per word and workgroup, and none for bits already
+// set there (8 same-address atomics per wave serialised in the L2: 0.4 ms
+// of byte256's alphabet pass once its waves stopped early)
+__device__ __forceinline__ void alphabet_reduce(const uint32_t* m, uint32_t* __restrict__ present) {
+    __shared__ uint32_t s_or[8];
+    if (threadIdx.x < 8) s_or[threadIdx.x] = 0;
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        uint32_t x = m[i];
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) x |= __shfl_xor(x, o, kWave);
+        if (lane_id() == 0 && x) atomicOr(&s_or[i], x);
+    }
+    __syncthreads();
+    if (threadIdx.x < 8) {
+        const uint32_t x = s_or[threadIdx.x];
+        if (x & ~__hip_atomic_load(&present[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+            atomicOr(&present[threadIdx.x], x);
+    }
+}
+
 // ---------------------------------------------------------------------------
 // alphabet presence: bit b of present[b >> 5] is set when byte b occurs.
 // Presence is all the dense codes need; it is kept in 8 registers per lane
@@ -894,25 +918,51 @@ __global__ __launch_bounds__(kBlock) void k_alphabet(const uint8_t* __restrict__
         }
         v = vn;
     }
-    // one global atomic per word and workgroup, and none for bits already
-    // set there (8 same-address atomics per wave serialised in the L2: 0.4 ms
-    // of byte256's alphabet pass once its waves stopped early)
-    __shared__ uint32_t s_or[8];
-    if (threadIdx.x < 8) s_or[threadIdx.x] = 0;
-    __syncthreads();
+    alphabet_reduce(m, present);
+}
+
+// The presence mask of a sample of the text (sa_alpha.h: ns of its nb
+// kAlphaBlock-byte blocks, the first and the last among them): one block per
+// workgroup and step, 16 bytes per lane, four blocks' loads in flight.  A
+// grid of a few workgroups per CU: they all end at about the same time, and
+// each ends in an atomic on the same words of present (2048 workgroups, one
+// block or two each: 0.028 ms at 1 GiB, most of it those atomics).  The first
+// bucket pass proves the alphabet the host derives from the mask
+// (k_split_text, alpha_bad).
+__global__ __launch_bounds__(kBlock) void k_alphabet_sample(const uint8_t* __restrict__ text, uint64_t n, uint64_t nb,
+                                                            uint64_t ns, uint32_t* __restrict__ present) {
+    static_assert(kBlock * 16 == (int)kAlphaBlock, "one 16-byte chunk per lane and block");
+    __shared__ uint32_t s_m[kBlock * 9];   // a private mask per lane, as k_alphabet
+    uint32_t* m = s_m + threadIdx.x * 9;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        uint32_t x = m[i];
+    for (int i = 0; i < 8; ++i) m[i] = 0;
+    auto add = [&](uint32_t b) { atomicOr(&m[b >> 5], 1u << (b & 31u)); };
+    const bool al16 = (((uintptr_t)text) & 15) == 0;
+    constexpr int kFlight = 4;
+    for (uint64_t j0 = blockIdx.x; j0 < ns; j0 += (uint64_t)kFlight * gridDim.x) {
+        uint4 v[kFlight];
+        uint64_t at[kFlight];   // the lane's chunk of block j0 + q gridDim.x (n: none)
 #pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) x |= __shfl_xor(x, o, kWave);
-        if (lane_id() == 0 && x) atomicOr(&s_or[i], x);
+        for (int q = 0; q < kFlight; ++q) {
+            const uint64_t j = j0 + (uint64_t)q * gridDim.x;
+            at[q] = j < ns ? alpha_block(j, nb, ns) * kAlphaBlock + threadIdx.x * 16u : n;
+            v[q] = make_uint4(0u, 0u, 0u, 0u);
+            if (al16 && at[q] + 16 <= n) v[q] = *reinterpret_cast<const uint4*>(text + at[q]);
+        }
+#pragma unroll
+        for (int q = 0; q < kFlight; ++q) {
+            if (al16 && at[q] + 16 <= n) {
+                const uint32_t w4[4] = {v[q].x, v[q].y, v[q].z, v[q].w};
+#pragma unroll
+                for (int w = 0; w < 4; ++w)
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) add((w4[w] >> (8 * b)) & 0xFFu);
+            } else {
+                for (uint64_t k = at[q]; k < n && k < at[q] + 16; ++k) add(text[k]);
+            }
+        }
     }
-    __syncthreads();
-    if (threadIdx.x < 8) {
-        const uint32_t x = s_or[threadIdx.x];
-        if (x & ~__hip_atomic_load(&present[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-            atomicOr(&present[threadIdx.x], x);
-    }
+    alphabet_reduce(m, present);
 }
 
 // ---------------------------------------------------------------------------

@@ -93,6 +93,9 @@ constexpr uint64_t kPadMaxN = 1ull << 31;
 // words[]: set by a per-group register sort that cannot finish its round
 // (k_usort_small: a group over kUsLimit; k_round2_windows)
 constexpr int kUsFlagWord = 12;
+// words[]: set by the first bucket pass when it stages a byte outside a
+// sampled alphabet (k_split_text alpha_bad); read back with the window list
+constexpr int kAlphaBadWord = 8;
 
 // bits of key1 + 1, the round-2 key of SrcUKey1 and k_round2_windows
 static uint32_t key1_bits(const BucketSpec& bs) {
@@ -289,7 +292,8 @@ static int round1_bucketed(sa_context* c, const uint8_t* d_text, uint64_t n, uin
     int rc = onesweep_prepare(c, s);
     if (rc) return rc;
     // [0..2] D, m, G of the fused segments, [5] largest window, [6] local-sort
-    // flags, [7] windows, [10] skewed windows
+    // flags, [7] windows, [8] a byte outside the sampled alphabet, [10] skewed
+    // windows
     SA_HIP(hipMemsetAsync(c->words, 0, 12, s));
     SA_HIP(hipMemsetAsync(c->words + 5, 0, 28, s));   // [5, 11]
     // digit totals of both bucket passes (one read of the text)
@@ -500,6 +504,8 @@ static int round1_bucketed(sa_context* c, const uint8_t* d_text, uint64_t n, uin
         const bool dna = SA_DNA_SWAR && c->dna && bp.bs.s + bp.bs.R + kItemsA - 1 <= 32 && 2 * bp.bs.s <= 32;
         // (sigma = 256: each position's key from the 8-byte window at it)
         const bool ident = SA_TEXT_IDENT && bp.bs.sigma == 256 && bp.bs.s + bp.bs.R <= 8 && bp.bs.s <= 4;
+        // codes from a sampled alphabet (build_packed): the pass proves them
+        uint32_t* const alpha_bad = c->alpha_prove && !listed ? c->words + kAlphaBadWord : nullptr;
         auto text_grid = [&](int block) {
             const uint64_t tile = (uint64_t)block * kItemsA;
             return (uint32_t)std::max<uint64_t>(
@@ -510,7 +516,7 @@ static int round1_bucketed(sa_context* c, const uint8_t* d_text, uint64_t n, uin
                        (const uint16_t*)c->code, bp.bs, (const uint32_t*)(padded ? pstart : os_base(c)),           \
                        os_tickets(c), c->keys[0], c->vals_alt, g_hi, cursor, m, blo, bhi,                          \
                        padded ? (const uint32_t*)pstart + 1 : nullptr, padded ? c->words + 11 : nullptr, hb, bp.ib, \
-                       stripes)
+                       stripes, alpha_bad)
         if (listed) {
             constexpr int kItemsL = SA_ITEMS_B, kListBlock = SA_LIST_BLOCK;
             const uint64_t tl = (uint64_t)kListBlock * kItemsL;
@@ -532,7 +538,7 @@ static int round1_bucketed(sa_context* c, const uint8_t* d_text, uint64_t n, uin
                        dim3(kSpBlock), 0, s, d_text, n, (const uint16_t*)c->code, bp.bs,                           \
                        (const uint32_t*)(padded ? pstart : os_base(c)), os_tickets(c), c->keys[0], c->vals_alt, g_hi, \
                        cursor, m, blo, bhi, padded ? (const uint32_t*)pstart + 1 : nullptr,                        \
-                       padded ? c->words + 11 : nullptr, hb, bp.ib, stripes)
+                       padded ? c->words + 11 : nullptr, hb, bp.ib, stripes, alpha_bad)
             if (bp.bs.powR1 * (uint64_t)bp.bs.sigma <= 0xFFFFFFFFull && !(((uint32_t)c->tune >> 28) & 1u))
                 SA_TEXT_NP2(true);
             else
@@ -554,7 +560,7 @@ static int round1_bucketed(sa_context* c, const uint8_t* d_text, uint64_t n, uin
                                dim3(text_grid(kSpBlock)), dim3(kSpBlock), 0, s, d_text, n, (const uint16_t*)c->code,
                                bp.bs, (const uint32_t*)(padded ? pstart : os_base(c)), os_tickets(c), c->keys[0],
                                c->vals_alt, g_hi, cursor, m, blo, bhi, padded ? (const uint32_t*)pstart + 1 : nullptr,
-                               padded ? c->words + 11 : nullptr, hb, bp.ib, stripes);
+                               padded ? c->words + 11 : nullptr, hb, bp.ib, stripes, alpha_bad);
         } else {
             SA_TEXT_PASS(false, false, kSpBlock, false, false);
         }
@@ -684,6 +690,13 @@ static int round1_bucketed(sa_context* c, const uint8_t* d_text, uint64_t n, uin
     SA_HIP(hipMemsetAsync(cnt_u, 0, (2 * nw + 2) * 4, s));
     SA_HIP(hipMemsetAsync(member, 0, (n + 31) / 32 * 4, s));
     SA_HIP(host_sync_event(c->ev[kSyncEv]));
+    // the sampled alphabet refuted: nothing else of this attempt counts (its
+    // foreign bytes went to digit 0, so segments and regions may have
+    // overflowed too); build_packed starts again with the exact alphabet
+    if (c->alpha_prove && c->host_words[kAlphaBadWord]) {
+        c->alpha_refuted = true;
+        return SA_OK;
+    }
     if (c->host_words[4]) return set_err(SA_E_INTERNAL, "radix look-back did not complete");
     if (padded && c->host_words[11]) {   // a digit outgrew its sampled segment: exact totals
         SA_TRACE("  bucketed round 1: padded segment overflow, again with exact digit totals");

@@ -21,6 +21,7 @@
 // processed and the look-back cannot deadlock.
 #pragma once
 #include <type_traits>
+#include "sa_alpha.h"
 #include "sa_bucket.h"
 #include "sa_onesweep.h"
 
@@ -441,7 +442,15 @@ __global__ __launch_bounds__(BLOCK, 2048 / BLOCK) void k_split_text(const uint8_
                                                          uint64_t m, uint32_t blo, uint32_t bhi,
                                                          const uint32_t* __restrict__ seg_end = nullptr,
                                                          uint32_t* __restrict__ ovf = nullptr, uint32_t pk_hb = 0,
-                                                         uint32_t pk_ib = 0, uint32_t stripes = 1) {
+                                                         uint32_t pk_ib = 0, uint32_t stripes = 1,
+                                                         uint32_t* __restrict__ alpha_bad = nullptr) {
+    // alpha_bad (non-null: `code` comes from a SAMPLE of the text, sa_alpha.h):
+    // every staged byte is tested against that alphabet -- DNA: the letter
+    // rebuilt from its digit; others: the byte map's entry of an absent byte
+    // is kAlphaAbsent, staged as digit 0 so that every bucket stays in range --
+    // and a foreign byte sets *alpha_bad (the build starts again with the
+    // exact alphabet).  IDENT, or any text with all 256 values: nothing to
+    // prove, the host passes null.
     // stripes > 1 (padded segments only): digit d's segment is cut into
     // `stripes` equal sub-segments and workgroup w claims in sub-segment
     // w % stripes from its own cursor cursor[(w % stripes) * RADIX + d]:
@@ -489,6 +498,8 @@ __global__ __launch_bounds__(BLOCK, 2048 / BLOCK) void k_split_text(const uint8_
     const uint8_t* s_dc = reinterpret_cast<const uint8_t*>(s_dcw);
     const uint32_t bspan = bhi - blo;
     bool over = false;
+    const bool prove = !IDENT && alpha_bad != nullptr;   // uniform
+    bool foreign = false;
 
     const uint32_t wave = wave_id(), lane = lane_id();
     const uint32_t dg = threadIdx.x;
@@ -505,7 +516,7 @@ __global__ __launch_bounds__(BLOCK, 2048 / BLOCK) void k_split_text(const uint8_
     cursor += stripe * RADIX;
     if (dg < 256u) {
         const uint32_t cv = code[dg];
-        s_map[dg] = (uint8_t)(cv ? cv - 1u : 0u);
+        s_map[dg] = (uint8_t)(prove ? alpha_map_entry(cv) : cv ? cv - 1u : 0u);
     }
     if (dg < (uint32_t)RADIX) s_cnt[dg] = 0;
     // thread 0: the next tile of its ticket and the tiles left in it
@@ -587,6 +598,37 @@ __global__ __launch_bounds__(BLOCK, 2048 / BLOCK) void k_split_text(const uint8_
 #else
 #define TEXT_STAMP(k)
 #endif
+    // a raw word's four digits (whole: every byte inside the text) and the
+    // test of its bytes: bad collects a set bit for a foreign one.  DNA: two
+    // VALU per word whether proving or not (with the exact alphabet no byte
+    // is foreign); the byte map holds markers under `prove` only.
+    auto map4 = [&](uint32_t w, uint32_t& bad) -> uint32_t {
+        if constexpr (DNA) {
+            const uint32_t o = dna_digits(w);
+            bad |= dna_foreign(w, o);
+            return o;
+        } else if constexpr (IDENT) {
+            return w;
+        } else {
+            uint32_t o = (uint32_t)s_map[w & 0xFFu] | ((uint32_t)s_map[(w >> 8) & 0xFFu] << 8) |
+                         ((uint32_t)s_map[(w >> 16) & 0xFFu] << 16) | ((uint32_t)s_map[w >> 24] << 24);
+            if (prove) {
+                const uint32_t a = absent_bytes(o);
+                bad |= a;
+                o = absent_to_zero(o, a);
+            }
+            return o;
+        }
+    };
+    // one byte's digit through the byte map (tiles that are not whole)
+    auto map1 = [&](uint32_t x, uint32_t& bad) -> uint32_t {
+        uint32_t v = s_map[x];
+        if (prove) {
+            bad |= v == kAlphaAbsent ? 1u : 0u;
+            v = v == kAlphaAbsent ? 0u : v;
+        }
+        return v;
+    };
     // stages tile tt from raw
     auto stage = [&](uint64_t tt) {
         const uint64_t tb = tt * TILE;
@@ -596,27 +638,21 @@ __global__ __launch_bounds__(BLOCK, 2048 / BLOCK) void k_split_text(const uint8_
         const bool whole = (uint32_t)tt < t_whole;   // uniform
         if constexpr (LD16) {
             if (dg < (uint32_t)NC) {
-                uint32_t o[4];
+                uint32_t o[4], bad = 0;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     o[i] = 0;
                     if (whole) {
-                        if constexpr (DNA)
-                            o[i] = ((raw[i] >> 1) ^ (raw[i] >> 2)) & 0x03030303u;
-                        else if constexpr (IDENT)
-                            o[i] = raw[i];
-                        else
-                            o[i] = (uint32_t)s_map[raw[i] & 0xFFu] | ((uint32_t)s_map[(raw[i] >> 8) & 0xFFu] << 8) |
-                                   ((uint32_t)s_map[(raw[i] >> 16) & 0xFFu] << 16) |
-                                   ((uint32_t)s_map[raw[i] >> 24] << 24);
+                        o[i] = map4(raw[i], bad);
                     } else {
 #pragma unroll
                         for (int q = 0; q < 4; ++q) {
                             const uint64_t pos = tb + 16ull * dg + 4ull * i + q;
-                            o[i] |= (pos < n ? (uint32_t)s_map[(raw[i] >> (8 * q)) & 0xFFu] : 0u) << (8 * q);
+                            o[i] |= (pos < n ? map1((raw[i] >> (8 * q)) & 0xFFu, bad) : 0u) << (8 * q);
                         }
                     }
                 }
+                foreign |= bad != 0u;
                 if constexpr (DNA) {
                     // byte i = the packed byte of text word 4 dg + i
                     uint32_t pw = 0;
@@ -634,22 +670,17 @@ __global__ __launch_bounds__(BLOCK, 2048 / BLOCK) void k_split_text(const uint8_
         for (int i = 0; i < WPT; ++i) {
             const uint32_t w = dg + i * BLOCK;
             if (w < (uint32_t)NW) {
-                uint32_t o = 0;
+                uint32_t o = 0, bad = 0;
                 if (whole) {
-                    if constexpr (DNA)
-                        o = ((raw[i] >> 1) ^ (raw[i] >> 2)) & 0x03030303u;
-                    else if constexpr (IDENT)
-                        o = raw[i];
-                    else
-                        o = (uint32_t)s_map[raw[i] & 0xFFu] | ((uint32_t)s_map[(raw[i] >> 8) & 0xFFu] << 8) |
-                            ((uint32_t)s_map[(raw[i] >> 16) & 0xFFu] << 16) | ((uint32_t)s_map[raw[i] >> 24] << 24);
+                    o = map4(raw[i], bad);
                 } else {
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         const uint64_t pos = tb + 4ull * w + q;
-                        o |= (pos < n ? (uint32_t)s_map[(raw[i] >> (8 * q)) & 0xFFu] : 0u) << (8 * q);
+                        o |= (pos < n ? map1((raw[i] >> (8 * q)) & 0xFFu, bad) : 0u) << (8 * q);
                     }
                 }
+                foreign |= bad != 0u;
                 s_dcw[w] = o;
                 if constexpr (DNA)
                     reinterpret_cast<uint8_t*>(s_pkw)[w] =
@@ -931,6 +962,7 @@ __global__ __launch_bounds__(BLOCK, 2048 / BLOCK) void k_split_text(const uint8_
     for (uint32_t i = dg; i < 1024u; i += BLOCK)
         if (s_hhi[i]) atomicAdd(&ghist_hi[i], s_hhi[i]);
     if (over && ovf) atomicOr(ovf, 1u);
+    if (foreign && alpha_bad) atomicOr(alpha_bad, 1u);
 #if SA_TEXT_PROF
     if (dg == 0 && (blockIdx.x == 0 || blockIdx.x == gridDim.x / 2))
         printf("k_split_text wg %u clk: stage %llu keys %llu claims %llu scatter %llu write %llu\n", blockIdx.x,

@@ -108,6 +108,17 @@ enum sa_kernel_kind {
                                            every listed window passes through it in ticket order (tests of the
                                            window-to-window hand-over at sizes an oracle sorts; phase times of one
                                            workgroup); the plan, the windows and the statistics stay the same */
+#define SA_DEBUG_NO_ALPHA_SAMPLE 0x10000u /* packed schedule: the alphabet always from the pass over the whole text,
+                                           never from a sample that the first bucket pass proves (A/B runs; callers
+                                           who want no speculative work: a text with a symbol in none of the sampled
+                                           blocks pays a wasted first and second pass before the exact re-run) */
+#define SA_DEBUG_ALPHA_SAMPLE_SMALL 0x20000u /* the sampled alphabet at any n, its sample the text's first 4096 bytes
+                                           only (tests: both outcomes at sizes an oracle sorts) */
+
+/* sa_stats.alphabet */
+#define SA_ALPHABET_EXACT 0    /* from a pass over the whole text */
+#define SA_ALPHABET_SAMPLED 1  /* from a sample, proven by the first bucket pass */
+#define SA_ALPHABET_REFUTED 2  /* a sample the first bucket pass refuted: the build ran again with the exact one */
 
 typedef struct {
     int32_t profile;        /* 1: time every launch with HIP events */
@@ -166,6 +177,7 @@ typedef struct {
                                             [1] one-bucket windows sorted by the fixed-span kernel, [2] windows
                                             sorted again with their measured span (several buckets, or keys
                                             clustered in one sub-bucket), [3] skewed windows (LSD kernel) */
+    int32_t alphabet;                    /* SA_ALPHABET_*: where the dense codes came from (packed schedule) */
 } sa_stats;
 
 typedef struct sa_context sa_context;
