@@ -30,6 +30,24 @@ def _as_bytes_array(text) -> np.ndarray:
     return np.ascontiguousarray(text, dtype=np.uint8)
 
 
+def _sa_array(sa) -> np.ndarray:
+    """Contiguous; uint32 / int32 (width 4) as they are, any other dtype as int64 (width 8)."""
+    s = np.ascontiguousarray(sa)
+    return s if s.dtype in (np.uint32, np.int32, np.int64) else s.astype(np.int64)
+
+
+def _stream(stream):
+    """A HIP stream handle (an int) as the void* of the C side; None: the null stream."""
+    return None if stream is None else ctypes.c_void_p(int(stream))
+
+
+def _find_mode(mode: str) -> int:
+    """The SA_FIND_* flags of ``mode``."""
+    if mode not in N.FIND_MODES:
+        raise ValueError(f"mode {mode!r}: one of {sorted(N.FIND_MODES)}")
+    return N.FIND_MODES[mode]
+
+
 SCHEDULES = {"packed": N.SCHEDULE_PACKED, "reference": N.SCHEDULE_REFERENCE}
 RADIX = {"onesweep": 0, "reduce_scan": 1}
 ROUND1 = {"auto": N.ROUND1_AUTO, "lsd": N.ROUND1_LSD, "bucketed": N.ROUND1_BUCKETED}
@@ -91,9 +109,7 @@ def build_suffix_array(text, width: int = 4, profile: bool = False, return_stats
 def check_suffix_array(text, sa) -> bool:
     """O(n) GPU validity check (replaces is_valid_suffix_array, :184-202)."""
     t = _as_bytes_array(text)
-    s = np.ascontiguousarray(sa)
-    if s.dtype not in (np.uint32, np.int32, np.int64):
-        s = s.astype(np.int64)
+    s = _sa_array(sa)
     if s.size != t.size:
         return False
     N.require_device()
@@ -112,9 +128,7 @@ def lcp_array(text, sa, width: int = 4):
     (width 4) or int64 (width 8), and lrs = (length, SA position) of the first
     r with the strictly largest lcp ((0, 0) when nothing repeats)."""
     t = _as_bytes_array(text)
-    s = np.ascontiguousarray(sa)
-    if s.dtype not in (np.uint32, np.int32, np.int64):
-        s = s.astype(np.int64)
+    s = _sa_array(sa)
     n = int(t.size)
     if s.size != n:
         raise ValueError(f"SA has {s.size} entries for a text of {n} bytes")
@@ -161,8 +175,7 @@ def _pack_patterns(patterns):
 
 def _find_host(t_ptr, n: int, sa_ptr, width: int, patterns, mode: str):
     """sa_find_ex over host pointers: (lo, hi) as int64 arrays."""
-    if mode not in N.FIND_MODES:
-        raise ValueError(f"mode {mode!r}: one of {sorted(N.FIND_MODES)}")
+    flags = _find_mode(mode)
     buf, off = _pack_patterns(patterns)
     nq = int(off.size) - 1
     lo = np.zeros(nq, dtype=np.uint64)
@@ -170,15 +183,13 @@ def _find_host(t_ptr, n: int, sa_ptr, width: int, patterns, mode: str):
     if nq:
         N.check(N.lib().sa_find_ex(t_ptr if n else None, n, sa_ptr if n else None, width,
                                    buf.ctypes.data if buf.size else None, off.ctypes.data, nq,
-                                   lo.ctypes.data, hi.ctypes.data, N.FIND_MODES[mode]), "sa_find")
+                                   lo.ctypes.data, hi.ctypes.data, flags), "sa_find")
     return lo.astype(np.int64), hi.astype(np.int64)
 
 
 def _text_and_sa(text, sa):
     t = _as_bytes_array(text)
-    s = np.ascontiguousarray(sa)
-    if s.dtype not in (np.uint32, np.int32, np.int64):
-        s = s.astype(np.int64)
+    s = _sa_array(sa)
     if s.size != t.size:
         raise ValueError(f"SA has {s.size} entries for a text of {t.size} bytes")
     return t, s
@@ -234,9 +245,7 @@ def locate_intervals(sa, lo, hi, max_hits: int = 0, order: str = "text", _chunks
     flags = _locate_flags(order, _chunks)
     if max_hits < 0:
         raise ValueError("max_hits is negative")
-    s = np.ascontiguousarray(sa)
-    if s.dtype not in (np.uint32, np.int32, np.int64):
-        s = s.astype(np.int64)
+    s = _sa_array(sa)
     lo = np.ascontiguousarray(lo, dtype=np.uint64).reshape(-1)
     hi = np.ascontiguousarray(hi, dtype=np.uint64).reshape(-1)
     if lo.size != hi.size:
@@ -266,8 +275,7 @@ def locate_batch(text, sa, patterns, max_hits: int = 0, order: str = "text", mod
 def _match_host(t_ptr, n: int, sa_ptr, width: int, patterns, mode: str, bounds: bool):
     """sa_match over host pointers: (length, lo, hi) as int64 arrays, or the
     lengths alone."""
-    if mode not in N.FIND_MODES:
-        raise ValueError(f"mode {mode!r}: one of {sorted(N.FIND_MODES)}")
+    flags = _find_mode(mode)
     buf, off = _pack_patterns(patterns)
     nq = int(off.size) - 1
     out = np.zeros((3 if bounds else 1, nq), dtype=np.uint64)
@@ -275,7 +283,7 @@ def _match_host(t_ptr, n: int, sa_ptr, width: int, patterns, mode: str, bounds: 
         N.check(N.lib().sa_match(t_ptr if n else None, n, sa_ptr if n else None, width,
                                  buf.ctypes.data if buf.size else None, off.ctypes.data, nq, out[0].ctypes.data,
                                  out[1].ctypes.data if bounds else None, out[2].ctypes.data if bounds else None,
-                                 N.FIND_MODES[mode]), "sa_match")
+                                 flags), "sa_match")
     out = out.astype(np.int64)
     return (out[0], out[1], out[2]) if bounds else out[0]
 
@@ -307,8 +315,7 @@ def matching_statistics(text, sa, query, max_len: int = 0, mode: str = "auto", b
     ``mode``: "auto" takes the one-query-per-lane kernel when no query can be
     longer than FIND_LANE_MAX bytes and the one-query-per-wavefront kernel
     otherwise; "lane" / "wave" force one."""
-    if mode not in N.FIND_MODES:
-        raise ValueError(f"mode {mode!r}: one of {sorted(N.FIND_MODES)}")
+    flags = _find_mode(mode)
     if max_len < 0:
         raise ValueError("max_len is negative")
     t, s = _text_and_sa(text, sa)
@@ -320,7 +327,7 @@ def matching_statistics(text, sa, query, max_len: int = 0, mode: str = "auto", b
         N.check(N.lib().sa_matching_stats(t.ctypes.data if n else None, n, s.ctypes.data if n else None,
                                           8 if s.dtype == np.int64 else 4, q.ctypes.data, m, int(max_len),
                                           out[0].ctypes.data, out[1].ctypes.data if bounds else None,
-                                          out[2].ctypes.data if bounds else None, N.FIND_MODES[mode]),
+                                          out[2].ctypes.data if bounds else None, flags),
                 "sa_matching_stats")
     out = out.astype(np.int64)
     return (out[0], out[1], out[2]) if bounds else out[0]
@@ -364,9 +371,7 @@ def inverse_suffix_array(sa, width: int = 4):
     is not a permutation of 0 .. n-1 raises SAError."""
     if width not in (4, 8):
         raise ValueError("width must be 4 or 8")
-    s = np.ascontiguousarray(sa)
-    if s.dtype not in (np.uint32, np.int32, np.int64):
-        s = s.astype(np.int64)
+    s = _sa_array(sa)
     n = int(s.size)
     if s.itemsize != width:   # the C entry point takes input and output at one width
         if width == 4 and n and (int(s.min()) < 0 or int(s.max()) >= n):
@@ -504,7 +509,7 @@ class DeviceBuilder:
               tune: int = 0) -> dict:
         """Build the SA of the n bytes at d_text into the n uint32 at d_sa."""
         st = N.SaStats()
-        s = None if stream is None else ctypes.c_void_p(int(stream))
+        s = _stream(stream)
         N.check(self.L.sa_build_device(self.ctx, self._ptr(d_text), n, self._ptr(d_sa), s,
                                        ctypes.byref(_opts(profile, schedule, init_chars, radix, round1, debug,
                                                           span_extra, tune)),
@@ -520,19 +525,19 @@ class DeviceBuilder:
 
     def generate_text(self, d_out, n: int, alphabet: bytes, seed: int = 1, stream=None) -> None:
         """Fill n device bytes with the seeded splitmix64 text."""
-        s = None if stream is None else ctypes.c_void_p(int(stream))
+        s = _stream(stream)
         N.check(self.L.sa_generate_text_device(self._ptr(d_out), n, seed, alphabet, len(alphabet), s),
                 "sa_generate_text_device")
 
     def check(self, d_text, n: int, d_sa, stream=None) -> bool:
-        s = None if stream is None else ctypes.c_void_p(int(stream))
+        s = _stream(stream)
         return bool(N.check(self.L.sa_check_device(self.ctx, self._ptr(d_text), n, self._ptr(d_sa), s),
                             "sa_check_device"))
 
     def lcp(self, d_text, n: int, d_sa, d_lcp, stream=None) -> tuple:
         """LCP of the SA at d_sa into the n uint32 at d_lcp; returns the longest
         repeated substring as (length, SA position)."""
-        s = None if stream is None else ctypes.c_void_p(int(stream))
+        s = _stream(stream)
         ln, pos = ctypes.c_uint64(), ctypes.c_uint64()
         N.check(self.L.sa_lcp_device(self.ctx, self._ptr(d_text), n, self._ptr(d_sa), self._ptr(d_lcp),
                                      ctypes.byref(ln), ctypes.byref(pos), s), "sa_lcp_device")
@@ -544,11 +549,10 @@ class DeviceBuilder:
         pattern q is bytes d_off[q] .. d_off[q + 1] (uint64, nq + 1 entries) of
         the pat_bytes at d_pat; [d_lo[q], d_hi[q]) (uint32) is its interval in
         the SA at d_sa.  Enqueued on ``stream``; does not wait for it."""
-        if mode not in N.FIND_MODES:
-            raise ValueError(f"mode {mode!r}: one of {sorted(N.FIND_MODES)}")
-        s = None if stream is None else ctypes.c_void_p(int(stream))
+        flags = _find_mode(mode)
+        s = _stream(stream)
         N.check(self.L.sa_find_device(self._ptr(d_text), n, self._ptr(d_sa), self._ptr(d_pat), pat_bytes,
-                                      self._ptr(d_off), nq, self._ptr(d_lo), self._ptr(d_hi), N.FIND_MODES[mode], s),
+                                      self._ptr(d_off), nq, self._ptr(d_lo), self._ptr(d_hi), flags, s),
                 "sa_find_device")
 
     def match(self, d_text, n: int, d_sa, d_pat, pat_bytes: int, d_off, nq: int, d_len, d_lo=None, d_hi=None,
@@ -559,13 +563,12 @@ class DeviceBuilder:
         [d_lo[q], d_hi[q]) that prefix's interval in the SA at d_sa.
         ``d_lo=None, d_hi=None`` asks for the lengths only.  Enqueued on
         ``stream``; does not wait for it."""
-        if mode not in N.FIND_MODES:
-            raise ValueError(f"mode {mode!r}: one of {sorted(N.FIND_MODES)}")
-        s = None if stream is None else ctypes.c_void_p(int(stream))
+        flags = _find_mode(mode)
+        s = _stream(stream)
         N.check(self.L.sa_match_device(self._ptr(d_text), n, self._ptr(d_sa), self._ptr(d_pat), pat_bytes,
                                        self._ptr(d_off), nq, self._ptr(d_len),
                                        None if d_lo is None else self._ptr(d_lo),
-                                       None if d_hi is None else self._ptr(d_hi), N.FIND_MODES[mode], s),
+                                       None if d_hi is None else self._ptr(d_hi), flags, s),
                 "sa_match_device")
 
     def matching_statistics(self, d_text, n: int, d_sa, d_query, m: int, d_len, d_lo=None, d_hi=None,
@@ -576,12 +579,11 @@ class DeviceBuilder:
         (to the end when max_len is 0) as match does.  ``d_lo=None,
         d_hi=None`` asks for the lengths only.  Enqueued on ``stream``; does
         not wait for it."""
-        if mode not in N.FIND_MODES:
-            raise ValueError(f"mode {mode!r}: one of {sorted(N.FIND_MODES)}")
-        s = None if stream is None else ctypes.c_void_p(int(stream))
+        flags = _find_mode(mode)
+        s = _stream(stream)
         N.check(self.L.sa_matching_stats_device(self._ptr(d_text), n, self._ptr(d_sa), self._ptr(d_query), m, max_len,
                                                 self._ptr(d_len), None if d_lo is None else self._ptr(d_lo),
-                                                None if d_hi is None else self._ptr(d_hi), N.FIND_MODES[mode], s),
+                                                None if d_hi is None else self._ptr(d_hi), flags, s),
                 "sa_matching_stats_device")
 
     def bwt(self, d_text, n: int, d_sa, d_bwt, d_stats=None, stream=None) -> None:
@@ -591,7 +593,7 @@ class DeviceBuilder:
         memory ([0] primary index, [1] runs, [2 + c] count of byte c), zeroed
         and filled by the call; None skips the statistics.  Enqueued on
         ``stream``; does not wait for it."""
-        s = None if stream is None else ctypes.c_void_p(int(stream))
+        s = _stream(stream)
         N.check(self.L.sa_bwt_device(self._ptr(d_text), n, self._ptr(d_sa), self._ptr(d_bwt),
                                      None if d_stats is None else self._ptr(d_stats), s), "sa_bwt_device")
 
@@ -599,7 +601,7 @@ class DeviceBuilder:
         """Inverse suffix array of the SA at d_sa into the n uint32 at d_isa
         (16-byte aligned, not d_sa): d_isa[d_sa[r]] = r (sa_inverse_device).
         Waits for ``stream``; raises SAError when d_sa is not a permutation."""
-        s = None if stream is None else ctypes.c_void_p(int(stream))
+        s = _stream(stream)
         N.check(self.L.sa_inverse_device(self.ctx, n, self._ptr(d_sa), self._ptr(d_isa), s), "sa_inverse_device")
 
     def locate(self, n: int, d_sa, d_lo, d_hi, nq: int, d_off, d_pos, pos_cap: int, max_hits: int = 0,
@@ -610,7 +612,7 @@ class DeviceBuilder:
         the total number of hits.  Positions are written only when the total
         fits pos_cap and d_pos is not None: call once with ``d_pos=None`` to
         size the output, allocate, and call again.  Waits for ``stream``."""
-        s = None if stream is None else ctypes.c_void_p(int(stream))
+        s = _stream(stream)
         total = ctypes.c_uint64()
         N.check(self.L.sa_locate_device(self.ctx, n, self._ptr(d_sa), self._ptr(d_lo), self._ptr(d_hi), nq,
                                         int(max_hits), _locate_flags(order, _chunks), self._ptr(d_off),

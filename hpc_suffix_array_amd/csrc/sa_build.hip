@@ -2103,141 +2103,12 @@ __global__ __launch_bounds__(kBlock) void k_gen_text(uint8_t* __restrict__ out, 
     }
 }
 
-// ---------------------------------------------------------------------------
-// Host <-> HBM copies of the host-pointer entry points (the reference's
-// read_file / create path, utils.c:6-48, hands over pageable malloc memory).
-// Pageable copies are staged by the HIP runtime one piece at a time; here a
-// ring of pinned chunks is filled by several host threads while the DMA
-// engine drains the previous chunk, so the PCIe link stays busy.  Memory the
-// caller already pinned (hipHostMalloc / hipHostRegister) is copied directly.
-// ---------------------------------------------------------------------------
-constexpr size_t kStageChunk = 32ull << 20;
-constexpr int kStageBufs = 3;
-
-static bool host_is_pinned(const void* p) {
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return a.type == hipMemoryTypeHost;
-}
-
-// memcpy of a large block by up to 8 threads (one core moves ~10 GB/s, the
-// link ~50 GB/s)
-static void par_memcpy(void* dst, const void* src, size_t bytes) {
-    const size_t kPiece = 4ull << 20;
-    const int th = (int)std::min<size_t>(8, (bytes + kPiece - 1) / kPiece);
-    if (th <= 1) {
-        std::memcpy(dst, src, bytes);
-        return;
-    }
-    std::vector<std::thread> pool;
-    const size_t per = (bytes + th - 1) / th;
-    for (int t = 0; t < th; ++t) {
-        const size_t a = (size_t)t * per, e = std::min(bytes, a + per);
-        if (a >= e) break;
-        pool.emplace_back([=] { std::memcpy((char*)dst + a, (const char*)src + a, e - a); });
-    }
-    for (auto& x : pool) x.join();
-}
-
-struct Staging {
-    void* buf[kStageBufs] = {nullptr, nullptr, nullptr};
-    hipEvent_t ev[kStageBufs] = {nullptr, nullptr, nullptr};
-    int make() {
-        for (int i = 0; i < kStageBufs; ++i) {
-            if (hipHostMalloc(&buf[i], kStageChunk, hipHostMallocDefault) != hipSuccess ||
-                hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) != hipSuccess) {
-                (void)hipGetLastError();
-                return set_err(SA_E_NOMEM, "pinned staging allocation failed");
-            }
-        }
-        return SA_OK;
-    }
-    ~Staging() {
-        for (int i = 0; i < kStageBufs; ++i) {
-            if (buf[i]) hipHostFree(buf[i]);
-            if (ev[i]) hipEventDestroy(ev[i]);
-        }
-    }
-};
-
-static int copy_h2d(void* d_dst, const void* h_src, size_t bytes, hipStream_t s) {
-    if (bytes == 0) return SA_OK;
-    if (bytes <= kStageChunk || host_is_pinned(h_src)) {
-        SA_HIP(hipMemcpyAsync(d_dst, h_src, bytes, hipMemcpyHostToDevice, s));
-        return SA_OK;
-    }
-    Staging st;
-    int rc = st.make();
-    if (rc) return rc;
-    size_t off = 0;
-    for (int k = 0; off < bytes; ++k, off += kStageChunk) {
-        const int b = k % kStageBufs;
-        const size_t len = std::min(kStageChunk, bytes - off);
-        if (k >= kStageBufs) SA_HIP(hipEventSynchronize(st.ev[b]));   // its previous DMA is done
-        par_memcpy(st.buf[b], (const char*)h_src + off, len);
-        SA_HIP(hipMemcpyAsync((char*)d_dst + off, st.buf[b], len, hipMemcpyHostToDevice, s));
-        SA_HIP(hipEventRecord(st.ev[b], s));
-    }
-    SA_HIP(host_sync(s));
-    return SA_OK;
-}
-
-// conv: 4 = raw u32 copy, 8 = widen u32 -> int64 into the host array
-static int copy_d2h(void* h_dst, const uint32_t* d_src, uint64_t count, int width, hipStream_t s) {
-    const size_t bytes = count * 4;
-    if (count == 0) return SA_OK;
-    if (width == 4 && (bytes <= kStageChunk || host_is_pinned(h_dst))) {
-        SA_HIP(hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, s));
-        SA_HIP(host_sync(s));
-        return SA_OK;
-    }
-    Staging st;
-    int rc = st.make();
-    if (rc) return rc;
-    const uint64_t per = kStageChunk / 4;
-    const uint64_t chunks = (count + per - 1) / per;
-    auto issue = [&](uint64_t k) -> int {
-        const int b = (int)(k % kStageBufs);
-        const uint64_t a = k * per, len = std::min(per, count - a);
-        SA_HIP(hipMemcpyAsync(st.buf[b], d_src + a, len * 4, hipMemcpyDeviceToHost, s));
-        SA_HIP(hipEventRecord(st.ev[b], s));
-        return SA_OK;
-    };
-    for (uint64_t k = 0; k < chunks && k + 1 < (uint64_t)kStageBufs; ++k)
-        if ((rc = issue(k))) return rc;
-    for (uint64_t k = 0; k < chunks; ++k) {
-        const int b = (int)(k % kStageBufs);
-        SA_HIP(hipEventSynchronize(st.ev[b]));
-        if (k + kStageBufs - 1 < chunks && (rc = issue(k + kStageBufs - 1))) return rc;
-        const uint64_t a = k * per, len = std::min(per, count - a);
-        if (width == 4) {
-            par_memcpy((uint32_t*)h_dst + a, st.buf[b], len * 4);
-        } else {
-            const uint32_t* src = (const uint32_t*)st.buf[b];
-            int64_t* o = (int64_t*)h_dst + a;
-            for (uint64_t i = 0; i < len; ++i) o[i] = src[i];
-        }
-    }
-    return SA_OK;
-}
-
-// process-wide context for the host-pointer entry points (lazy, locked)
-static std::mutex g_mu;
-static sa_context* g_ctx = nullptr;
-
-static int global_ctx(uint64_t n, sa_context** out) {
-    if (!g_ctx) {
-        int rc = sa_context_create(0, n, &g_ctx);
-        if (rc) return rc;
-    }
-    *out = g_ctx;
-    return ensure_capacity(g_ctx, n);
-}
-
 }  // namespace sa
+
+// the host side of the host-pointer entry points: staged copies, the
+// process-wide context, device buffers freed by scope, and the host forms of
+// sa_build_ex, sa_check and sa_lcp
+#include "sa_host.h"
 
 // batched pattern search (sa_find, sa_find_device): kernels, launches and its
 // entry points
@@ -2362,100 +2233,12 @@ int sa_lcp_device(sa_context* ctx, const uint8_t* d_text, uint64_t n, const uint
 
 int sa_lcp(const uint8_t* text, uint64_t n, const void* sa, int sa_width, void* lcp_out, uint64_t* lrs_len,
            uint64_t* lrs_pos) {
-    if (lrs_len) *lrs_len = 0;
-    if (lrs_pos) *lrs_pos = 0;
-    if (sa_width != 4 && sa_width != 8) return set_err(SA_E_INVALID, "sa_width must be 4 or 8");
-    if (n == 0) return SA_OK;
-    if (!text || !sa || !lcp_out) return set_err(SA_E_INVALID, "NULL host pointer");
-    if (n > 0xFFFFFFFFull) return set_err(SA_E_INVALID, "n too large");
-    std::vector<uint32_t> narrow;
-    const void* src = sa;
-    if (sa_width == 8) {
-        narrow.resize(n);
-        const int64_t* w = (const int64_t*)sa;
-        for (uint64_t i = 0; i < n; ++i) {
-            if (w[i] < 0 || (uint64_t)w[i] >= n) return set_err(SA_E_INVALID, "SA entry out of range");
-            narrow[i] = (uint32_t)w[i];
-        }
-        src = narrow.data();
-    }
-    std::lock_guard<std::mutex> lk(g_mu);
-    sa_context* c = nullptr;
-    int rc = global_ctx(n, &c);
-    if (rc) return rc;
-    uint8_t* d_text = nullptr;
-    uint32_t* d_sa = nullptr;
-    uint32_t* d_lcp = nullptr;
-    if (hipMalloc(&d_text, align_up(n, 256)) != hipSuccess || hipMalloc(&d_sa, align_up(n, 64) * 4) != hipSuccess ||
-        hipMalloc(&d_lcp, align_up(n, 64) * 4) != hipSuccess) {
-        hipFree(d_text);
-        hipFree(d_sa);
-        (void)hipGetLastError();
-        return set_err(SA_E_NOMEM, "device allocation failed");
-    }
-    if (copy_h2d(d_text, text, n, nullptr) != SA_OK || copy_h2d(d_sa, src, n * 4, nullptr) != SA_OK ||
-        host_sync(nullptr) != hipSuccess)
-        rc = set_err(SA_E_HIP, "H2D copy failed: %s", g_err.c_str());
-    // the checker rejects a non-permutation before PHI would scatter through it
-    if (rc == SA_OK) {
-        rc = check_device(c, d_text, n, d_sa, nullptr);
-        if (rc == 0) rc = set_err(SA_E_INVALID, "not a valid suffix array of the text");
-        else if (rc == 1) rc = SA_OK;
-    }
-    if (rc == SA_OK) rc = lcp_device(c, d_text, n, d_sa, d_lcp, lrs_len, lrs_pos, nullptr);
-    if (rc == SA_OK) {
-        rc = copy_d2h(lcp_out, d_lcp, n, sa_width, nullptr);
-    }
-    hipFree(d_text);
-    hipFree(d_sa);
-    hipFree(d_lcp);
-    return rc;
+    return lcp_host(text, n, sa, sa_width, lcp_out, lrs_len, lrs_pos);
 }
 
 int sa_build_ex(const uint8_t* text, uint64_t n, void* sa_out, int sa_width, const sa_opts* opts,
                 sa_stats* stats) {
-    if (sa_width != 4 && sa_width != 8) return set_err(SA_E_INVALID, "sa_width must be 4 or 8");
-    if (n && (!text || !sa_out)) return set_err(SA_E_INVALID, "NULL host pointer");
-    if (n == 0) {
-        if (stats) { std::memset(stats, 0, sizeof *stats); stats->n_kinds = SA_K_COUNT; }
-        return SA_OK;
-    }
-    std::lock_guard<std::mutex> lk(g_mu);
-    sa_context* c = nullptr;
-    SA_TRACE("sa_build_ex n=%llu", (unsigned long long)n);
-    int rc = global_ctx(n, &c);
-    SA_TRACE("global ctx rc=%d", rc);
-    if (rc) return rc;
-    uint8_t* d_text = nullptr;
-    uint32_t* d_sa = nullptr;
-    if (hipMalloc(&d_text, align_up(n, 256)) != hipSuccess || hipMalloc(&d_sa, align_up(n, 64) * 4) != hipSuccess) {
-        hipFree(d_text);
-        (void)hipGetLastError();
-        return set_err(SA_E_NOMEM, "device allocation of text/SA failed");
-    }
-    SA_TRACE("text/sa allocated");
-    hipStream_t s = nullptr;
-    // PCIe legs timed on the host clock (pinned staging overlaps host copies
-    // with the DMA; sa_stats reports them apart from total_ms)
-    auto t0 = std::chrono::steady_clock::now();
-    rc = copy_h2d(d_text, text, n, s);
-    if (rc == SA_OK) SA_HIP(host_sync(s));
-    auto t1 = std::chrono::steady_clock::now();
-    const double h2d = std::chrono::duration<double, std::milli>(t1 - t0).count();
-    if (rc == SA_OK) rc = build_device(c, d_text, n, d_sa, s, opts, stats);
-    double d2h = 0.0;
-    if (rc == SA_OK) {
-        t0 = std::chrono::steady_clock::now();
-        rc = copy_d2h(sa_out, d_sa, n, sa_width, s);
-        d2h = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-    if (stats) {
-        stats->h2d_ms = h2d;
-        stats->d2h_ms = d2h;
-    }
-    hipFree(d_text);
-    hipFree(d_sa);
-    return rc;
+    return build_host(text, n, sa_out, sa_width, opts, stats);
 }
 
 // dst[idx[i] - base] = src[i]; indices outside [base, base + dst_n) are
@@ -2887,40 +2670,7 @@ int sa_dist_refine(sa_context* ctx, uint64_t h, const uint64_t* d_ans, uint32_t*
 }
 
 int sa_check(const uint8_t* text, uint64_t n, const void* sa, int sa_width) {
-    if (sa_width != 4 && sa_width != 8) return set_err(SA_E_INVALID, "sa_width must be 4 or 8");
-    if (n == 0) return 1;
-    if (!text || !sa) return set_err(SA_E_INVALID, "NULL host pointer");
-    if (n > 0xFFFFFFFFull) return set_err(SA_E_INVALID, "n too large");
-    std::vector<uint32_t> narrow;
-    const void* src = sa;
-    if (sa_width == 8) {
-        narrow.resize(n);
-        const int64_t* w = (const int64_t*)sa;
-        for (uint64_t i = 0; i < n; ++i) {
-            if (w[i] < 0 || (uint64_t)w[i] >= n) return 0;
-            narrow[i] = (uint32_t)w[i];
-        }
-        src = narrow.data();
-    }
-    std::lock_guard<std::mutex> lk(g_mu);
-    sa_context* c = nullptr;
-    int rc = global_ctx(n, &c);
-    if (rc) return rc;
-    uint8_t* d_text = nullptr;
-    uint32_t* d_sa = nullptr;
-    if (hipMalloc(&d_text, align_up(n, 256)) != hipSuccess || hipMalloc(&d_sa, align_up(n, 64) * 4) != hipSuccess) {
-        hipFree(d_text);
-        (void)hipGetLastError();
-        return set_err(SA_E_NOMEM, "device allocation failed");
-    }
-    rc = SA_OK;
-    if (copy_h2d(d_text, text, n, nullptr) != SA_OK || copy_h2d(d_sa, src, n * 4, nullptr) != SA_OK ||
-        host_sync(nullptr) != hipSuccess)
-        rc = set_err(SA_E_HIP, "H2D copy failed: %s", g_err.c_str());
-    if (rc == SA_OK) rc = check_device(c, d_text, n, d_sa, nullptr);
-    hipFree(d_text);
-    hipFree(d_sa);
-    return rc;
+    return check_host(text, n, sa, sa_width);
 }
 
 }  // extern "C"

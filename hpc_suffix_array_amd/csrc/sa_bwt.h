@@ -37,6 +37,10 @@
 // Measured times, the cost of the statistics and the A/B run of the
 // non-temporal SA loads and output stores (SA_BWT_NT=0 builds the plain
 // variant): scripts/bench_bwt.py, DESIGN.md section 12, BASELINE.md "BWT".
+//
+// The HIP part needs sa_host.h before it (the host forms' staging, buffers,
+// checks and the process-wide context), and with it sa_build.hip's set_err /
+// SA_HIP / SA_TRY and the checker's permutation passes.
 #pragma once
 #include <stdint.h>
 
@@ -252,61 +256,32 @@ static int bwt_device(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa, u
     return SA_OK;
 }
 
-// the checks the host forms share: width, n, and a width-8 SA narrowed to 32
-// bits (entries outside [0, n) rejected); *src = the 32-bit entries
-static int narrow_sa(const void* sa, uint64_t n, int sa_width, std::vector<uint32_t>& narrow, const void** src) {
-    *src = sa;
-    if (sa_width == 8) {
-        narrow.resize(n);
-        const int64_t* w = (const int64_t*)sa;
-        for (uint64_t i = 0; i < n; ++i) {
-            if (w[i] < 0 || (uint64_t)w[i] >= n) return set_err(SA_E_INVALID, "SA entry out of range");
-            narrow[i] = (uint32_t)w[i];
-        }
-        *src = narrow.data();
-    }
-    return SA_OK;
-}
-
-// host in, host out (sa_bwt); every device buffer is freed on every path
+// host in, host out (sa_bwt), over the steps of sa_host.h
 static int bwt_host(const uint8_t* text, uint64_t n, const void* sa, int sa_width, uint8_t* bwt_out,
                     uint64_t* stats_out) {
     if (stats_out) std::memset(stats_out, 0, SA_BWT_STATS * 8);
-    if (sa_width != 4 && sa_width != 8) return set_err(SA_E_INVALID, "sa_width must be 4 or 8");
-    if (n > 0xFFFFFFFFull) return set_err(SA_E_INVALID, "n too large");
+    SA_TRY(check_width(sa_width));
+    SA_TRY(check_n32(n));
     if (n == 0) return SA_OK;
     if (!text || !sa || !bwt_out) return set_err(SA_E_INVALID, "NULL host pointer");
     std::vector<uint32_t> narrow;
     const void* src = nullptr;
     SA_TRY(narrow_sa(sa, n, sa_width, narrow, &src));
-    if (sa_device_count() <= 0) return set_err(SA_E_HIP, "no HIP device visible (libsa_hip needs an MI355X)");
-    void* d[4] = {nullptr, nullptr, nullptr, nullptr};   // text, sa, bwt, stats
-    const size_t bytes[4] = {(size_t)align_up(n, 256), (size_t)align_up(n, 64) * 4, (size_t)align_up(n, 256),
-                             (size_t)SA_BWT_STATS * 8};
-    int rc = SA_OK;
-    for (int i = 0; i < 4 && rc == SA_OK; ++i)
-        if (hipMalloc(&d[i], bytes[i]) != hipSuccess) {
-            (void)hipGetLastError();
-            rc = set_err(SA_E_NOMEM, "device allocation failed");
-        }
-    if (rc == SA_OK) {
-        if (copy_h2d(d[0], text, n, nullptr) != SA_OK || copy_h2d(d[1], src, n * 4, nullptr) != SA_OK ||
-            host_sync(nullptr) != hipSuccess)
-            rc = set_err(SA_E_HIP, "H2D copy failed: %s", g_err.c_str());
-    }
-    if (rc == SA_OK)
-        rc = bwt_device((const uint8_t*)d[0], n, (const uint32_t*)d[1], (uint8_t*)d[2],
-                        stats_out ? (uint64_t*)d[3] : nullptr, nullptr);
-    if (rc == SA_OK) {
-        if (hipMemcpyAsync(bwt_out, d[2], n, hipMemcpyDeviceToHost, nullptr) != hipSuccess ||
-            (stats_out &&
-             hipMemcpyAsync(stats_out, d[3], SA_BWT_STATS * 8, hipMemcpyDeviceToHost, nullptr) != hipSuccess) ||
-            host_sync(nullptr) != hipSuccess)
-            rc = set_err(SA_E_HIP, "BWT or D2H copy failed: %s", hipGetErrorString(hipGetLastError()));
-    }
-    for (int i = 0; i < 4; ++i)
-        if (d[i]) hipFree(d[i]);
-    return rc;
+    SA_TRY(need_device());
+    DevBuf d_text, d_sa, d_bwt, d_stats;
+    SA_TRY(d_text.alloc(align_up(n, 256)));
+    SA_TRY(d_sa.alloc(align_up(n, 64) * 4));
+    SA_TRY(d_bwt.alloc(align_up(n, 256)));
+    SA_TRY(d_stats.alloc(SA_BWT_STATS * 8));
+    SA_TRY(upload({{d_text.p, text, n}, {d_sa.p, src, n * 4}}));
+    SA_TRY(bwt_device(d_text.as<uint8_t>(), n, d_sa.as<uint32_t>(), d_bwt.as<uint8_t>(),
+                      stats_out ? d_stats.as<uint64_t>() : nullptr, nullptr));
+    if (hipMemcpyAsync(bwt_out, d_bwt.p, n, hipMemcpyDeviceToHost, nullptr) != hipSuccess ||
+        (stats_out &&
+         hipMemcpyAsync(stats_out, d_stats.p, SA_BWT_STATS * 8, hipMemcpyDeviceToHost, nullptr) != hipSuccess) ||
+        host_sync(nullptr) != hipSuccess)
+        return set_err(SA_E_HIP, "BWT or D2H copy failed: %s", hipGetErrorString(hipGetLastError()));
+    return SA_OK;
 }
 
 // ISA by the coalesced permutation (sa_check.h pass A's pairs under LCP's
@@ -343,34 +318,25 @@ static int inverse_device(sa_context* c, uint64_t n, const uint32_t* d_sa, uint3
     return SA_OK;
 }
 
-// host in, host out (sa_inverse)
+// host in, host out (sa_inverse), over the steps of sa_host.h
 static int inverse_host(const void* sa, uint64_t n, int sa_width, void* isa_out) {
-    if (sa_width != 4 && sa_width != 8) return set_err(SA_E_INVALID, "sa_width must be 4 or 8");
-    if (n > 0xFFFFFFFFull) return set_err(SA_E_INVALID, "n too large");
+    SA_TRY(check_width(sa_width));
+    SA_TRY(check_n32(n));
     if (n == 0) return SA_OK;
     if (!sa || !isa_out) return set_err(SA_E_INVALID, "NULL host pointer");
     std::vector<uint32_t> narrow;
     const void* src = nullptr;
     SA_TRY(narrow_sa(sa, n, sa_width, narrow, &src));
-    if (sa_device_count() <= 0) return set_err(SA_E_HIP, "no HIP device visible (libsa_hip needs an MI355X)");
+    SA_TRY(need_device());
     std::lock_guard<std::mutex> lk(g_mu);
     sa_context* c = nullptr;
-    int rc = global_ctx(n, &c);
-    if (rc) return rc;
-    uint32_t* d_sa = nullptr;
-    uint32_t* d_isa = nullptr;
-    if (hipMalloc(&d_sa, align_up(n, 64) * 4) != hipSuccess || hipMalloc(&d_isa, align_up(n, 64) * 4) != hipSuccess) {
-        hipFree(d_sa);
-        (void)hipGetLastError();
-        return set_err(SA_E_NOMEM, "device allocation failed");
-    }
-    if (copy_h2d(d_sa, src, n * 4, nullptr) != SA_OK || host_sync(nullptr) != hipSuccess)
-        rc = set_err(SA_E_HIP, "H2D copy failed: %s", g_err.c_str());
-    if (rc == SA_OK) rc = inverse_device(c, n, d_sa, d_isa, nullptr);
-    if (rc == SA_OK) rc = copy_d2h(isa_out, d_isa, n, sa_width, nullptr);
-    hipFree(d_sa);
-    hipFree(d_isa);
-    return rc;
+    SA_TRY(global_ctx(n, &c));
+    DevBuf d_sa, d_isa;
+    SA_TRY(d_sa.alloc(align_up(n, 64) * 4));
+    SA_TRY(d_isa.alloc(align_up(n, 64) * 4));
+    SA_TRY(upload({{d_sa.p, src, n * 4}}));
+    SA_TRY(inverse_device(c, n, d_sa.as<uint32_t>(), d_isa.as<uint32_t>(), nullptr));
+    return copy_d2h(isa_out, d_isa.as<uint32_t>(), n, sa_width, nullptr);
 }
 
 }  // namespace sa

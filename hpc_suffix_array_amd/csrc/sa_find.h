@@ -24,6 +24,8 @@
 //     descent only moves right (a pattern near the top of the order, a text of
 //     one symbol) and every probe starts again at byte 0.
 // The first part of this header compiles with g++ (tests/cpp/find_check.cpp).
+// The HIP part needs sa_host.h before it (the host form's staging, buffers
+// and checks), and with it sa_build.hip's set_err / SA_HIP / SA_TRY.
 #pragma once
 #include <stdint.h>
 
@@ -279,67 +281,33 @@ static int find_device(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa, 
     return SA_OK;
 }
 
-// host in, host out (sa_find / sa_find_ex); every device buffer is freed on
-// every path
+// host in, host out (sa_find / sa_find_ex), over the steps of sa_host.h
 static int find_host(const uint8_t* text, uint64_t n, const void* sa, int sa_width, const uint8_t* pat,
                      const uint64_t* pat_off, uint64_t nq, uint64_t* lo_out, uint64_t* hi_out, uint32_t flags) {
-    if (sa_width != 4 && sa_width != 8) return set_err(SA_E_INVALID, "sa_width must be 4 or 8");
+    SA_TRY(check_width(sa_width));
     if (flags > SA_FIND_WAVE) return set_err(SA_E_INVALID, "flags must be 0, SA_FIND_LANE or SA_FIND_WAVE");
     if (nq == 0) return SA_OK;
     if (!pat_off || !lo_out || !hi_out || (n && (!text || !sa))) return set_err(SA_E_INVALID, "NULL host pointer");
-    if (n > 0xFFFFFFFFull) return set_err(SA_E_INVALID, "n too large");
+    SA_TRY(check_n32(n));
     for (uint64_t q = 0; q < nq; ++q)
         if (pat_off[q] > pat_off[q + 1]) return set_err(SA_E_INVALID, "pattern offsets decrease at %llu", (unsigned long long)q);
     const uint64_t pat_bytes = pat_off[nq];
     if (pat_bytes && !pat) return set_err(SA_E_INVALID, "NULL host pointer");
     std::vector<uint32_t> narrow;
-    const void* src = sa;
-    if (sa_width == 8) {
-        narrow.resize(n);
-        const int64_t* w = (const int64_t*)sa;
-        for (uint64_t i = 0; i < n; ++i) {
-            if (w[i] < 0 || (uint64_t)w[i] >= n) return set_err(SA_E_INVALID, "SA entry out of range");
-            narrow[i] = (uint32_t)w[i];
-        }
-        src = narrow.data();
-    }
-    if (sa_device_count() <= 0) return set_err(SA_E_HIP, "no HIP device visible (libsa_hip needs an MI355X)");
-    void* d[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // text, sa, pat, off, lo, hi
-    const size_t bytes[6] = {(size_t)align_up(n + 1, 256),       (size_t)align_up(n + 1, 64) * 4,
-                             (size_t)align_up(pat_bytes + 1, 256), (size_t)(nq + 1) * 8,
-                             (size_t)nq * 4,                      (size_t)nq * 4};
-    int rc = SA_OK;
-    for (int i = 0; i < 6 && rc == SA_OK; ++i)
-        if (hipMalloc(&d[i], bytes[i]) != hipSuccess) {
-            (void)hipGetLastError();
-            rc = set_err(SA_E_NOMEM, "device allocation failed");
-        }
-    std::vector<uint32_t> res;
-    if (rc == SA_OK) {
-        if (copy_h2d(d[0], text, n, nullptr) != SA_OK || copy_h2d(d[1], src, n * 4, nullptr) != SA_OK ||
-            copy_h2d(d[2], pat, pat_bytes, nullptr) != SA_OK || copy_h2d(d[3], pat_off, (nq + 1) * 8, nullptr) != SA_OK ||
-            host_sync(nullptr) != hipSuccess)
-            rc = set_err(SA_E_HIP, "H2D copy failed: %s", g_err.c_str());
-    }
-    if (rc == SA_OK)
-        rc = find_device((const uint8_t*)d[0], n, (const uint32_t*)d[1], (const uint8_t*)d[2], pat_bytes,
-                         (const uint64_t*)d[3], nq, (uint32_t*)d[4], (uint32_t*)d[5], flags, nullptr);
-    if (rc == SA_OK) {
-        res.resize(2 * nq);
-        if (hipMemcpyAsync(res.data(), d[4], nq * 4, hipMemcpyDeviceToHost, nullptr) != hipSuccess ||
-            hipMemcpyAsync(res.data() + nq, d[5], nq * 4, hipMemcpyDeviceToHost, nullptr) != hipSuccess ||
-            host_sync(nullptr) != hipSuccess) {
-            rc = set_err(SA_E_HIP, "search or D2H copy failed: %s", hipGetErrorString(hipGetLastError()));
-        }
-    }
-    for (int i = 0; i < 6; ++i)
-        if (d[i]) hipFree(d[i]);
-    if (rc != SA_OK) return rc;
-    for (uint64_t q = 0; q < nq; ++q) {
-        lo_out[q] = res[q];
-        hi_out[q] = res[nq + q];
-    }
-    return SA_OK;
+    const void* src = nullptr;
+    SA_TRY(narrow_sa(sa, n, sa_width, narrow, &src));
+    SA_TRY(need_device());
+    DevBuf d_text, d_sa, d_pat, d_off, d_lo, d_hi;
+    SA_TRY(d_text.alloc(align_up(n + 1, 256)));
+    SA_TRY(d_sa.alloc(align_up(n + 1, 64) * 4));
+    SA_TRY(d_pat.alloc(align_up(pat_bytes + 1, 256)));
+    SA_TRY(d_off.alloc((nq + 1) * 8));
+    SA_TRY(d_lo.alloc(nq * 4));
+    SA_TRY(d_hi.alloc(nq * 4));
+    SA_TRY(upload({{d_text.p, text, n}, {d_sa.p, src, n * 4}, {d_pat.p, pat, pat_bytes}, {d_off.p, pat_off, (nq + 1) * 8}}));
+    SA_TRY(find_device(d_text.as<uint8_t>(), n, d_sa.as<uint32_t>(), d_pat.as<uint8_t>(), pat_bytes,
+                       d_off.as<uint64_t>(), nq, d_lo.as<uint32_t>(), d_hi.as<uint32_t>(), flags, nullptr));
+    return download_u64({{lo_out, d_lo.as<uint32_t>()}, {hi_out, d_hi.as<uint32_t>()}}, nq);
 }
 
 }  // namespace sa

@@ -42,6 +42,9 @@
 // the split of an output range for 16-byte stores) compiles on the host:
 // tests/cpp/locate_check.cpp checks it against brute force.
 // Measurements and the resource report: DESIGN.md section 13.
+// The HIP part needs sa_host.h before it (the host form's staging, buffers,
+// checks and the process-wide context), and sa_build.hip's scan_i64 and
+// sa_sort_pairs_device.
 #pragma once
 #include <stdint.h>
 
@@ -574,11 +577,12 @@ static int locate_device(sa_context* c, uint64_t n, const uint32_t* d_sa, const 
     return SA_OK;
 }
 
-// host in, host out (sa_locate): the offsets and the total are the host's own
+// host in, host out (sa_locate), over the steps of sa_host.h: the offsets and
+// the total are the host's own
 static int locate_host(const void* sa, uint64_t n, int sa_width, const uint64_t* lo, const uint64_t* hi, uint64_t nq,
                        uint64_t max_hits, uint32_t flags, uint64_t* off_out, void* pos_out, uint64_t pos_cap) {
-    if (sa_width != 4 && sa_width != 8) return set_err(SA_E_INVALID, "sa_width must be 4 or 8");
-    if (n > 0xFFFFFFFFull) return set_err(SA_E_INVALID, "n too large");
+    SA_TRY(check_width(sa_width));
+    SA_TRY(check_n32(n));
     if (nq > 0xFFFFFFFFull) return set_err(SA_E_INVALID, "nq too large");
     if (flags & ~(uint32_t)(SA_LOCATE_SA_ORDER | SA_LOCATE_SMALL_CHUNKS))
         return set_err(SA_E_INVALID, "unknown flags %#x", flags);
@@ -602,8 +606,8 @@ static int locate_host(const void* sa, uint64_t n, int sa_width, const uint64_t*
     SA_TRY(narrow_sa(sa, n, sa_width, narrow, &src));
     if (total == 0) return SA_OK;
     if (!pos_out) return set_err(SA_E_INVALID, "pos_out is NULL");
-    if (sa_device_count() <= 0) return set_err(SA_E_HIP, "no HIP device visible (libsa_hip needs an MI355X)");
-    std::vector<uint32_t> lh(2 * nq);
+    SA_TRY(need_device());
+    std::vector<uint32_t> lh(2 * nq);   // lo | hi, one upload
     for (uint64_t q = 0; q < nq; ++q) {
         lh[q] = (uint32_t)lo[q];
         lh[nq + q] = (uint32_t)hi[q];
@@ -611,31 +615,19 @@ static int locate_host(const void* sa, uint64_t n, int sa_width, const uint64_t*
     std::lock_guard<std::mutex> lk(g_mu);
     sa_context* c = nullptr;
     SA_TRY(global_ctx(std::max<uint64_t>(n, 1), &c));
-    void* d[4] = {nullptr, nullptr, nullptr, nullptr};   // sa, lo | hi, off, pos
-    const size_t bytes[4] = {(size_t)align_up(n, 64) * 4, (size_t)align_up(2 * nq, 64) * 4,
-                             (size_t)align_up(nq + 1, 64) * 8, (size_t)align_up(total, 64) * 4};
-    int rc = SA_OK;
-    for (int i = 0; i < 4 && rc == SA_OK; ++i)
-        if (hipMalloc(&d[i], bytes[i]) != hipSuccess) {
-            (void)hipGetLastError();
-            rc = set_err(SA_E_NOMEM, "device allocation failed");
-        }
-    if (rc == SA_OK) {
-        if (copy_h2d(d[0], src, n * 4, nullptr) != SA_OK || copy_h2d(d[1], lh.data(), 2 * nq * 4, nullptr) != SA_OK ||
-            host_sync(nullptr) != hipSuccess)
-            rc = set_err(SA_E_HIP, "H2D copy failed: %s", g_err.c_str());
-    }
+    DevBuf d_sa, d_lh, d_off, d_pos;
+    SA_TRY(d_sa.alloc(align_up(n, 64) * 4));
+    SA_TRY(d_lh.alloc(align_up(2 * nq, 64) * 4));
+    SA_TRY(d_off.alloc(align_up(nq + 1, 64) * 8));
+    SA_TRY(d_pos.alloc(align_up(total, 64) * 4));
+    SA_TRY(upload({{d_sa.p, src, n * 4}, {d_lh.p, lh.data(), 2 * nq * 4}}));
     uint64_t got = 0;
-    if (rc == SA_OK)
-        rc = locate_device(c, n, (const uint32_t*)d[0], (const uint32_t*)d[1], (const uint32_t*)d[1] + nq, nq, max_hits,
-                           flags, (uint64_t*)d[2], (uint32_t*)d[3], total, &got, nullptr);
-    if (rc == SA_OK && got != total)
-        rc = set_err(SA_E_INTERNAL, "locate: the device counted %llu hits, the host %llu", (unsigned long long)got,
-                     (unsigned long long)total);
-    if (rc == SA_OK) rc = copy_d2h(pos_out, (const uint32_t*)d[3], total, sa_width, nullptr);
-    for (int i = 0; i < 4; ++i)
-        if (d[i]) hipFree(d[i]);
-    return rc;
+    SA_TRY(locate_device(c, n, d_sa.as<uint32_t>(), d_lh.as<uint32_t>(), d_lh.as<uint32_t>() + nq, nq, max_hits, flags,
+                         d_off.as<uint64_t>(), d_pos.as<uint32_t>(), total, &got, nullptr));
+    if (got != total)
+        return set_err(SA_E_INTERNAL, "locate: the device counted %llu hits, the host %llu", (unsigned long long)got,
+                       (unsigned long long)total);
+    return copy_d2h(pos_out, d_pos.as<uint32_t>(), total, sa_width, nullptr);
 }
 
 }  // namespace sa

@@ -24,6 +24,8 @@
 // descent keeps where each end stood before its shared length last grew:
 // everything further out shares less than len.
 // The first part of this header compiles with g++ (tests/cpp/match_check.cpp).
+// The HIP part needs sa_host.h before it (the host form's staging, buffers
+// and checks), and with it sa_build.hip's set_err / SA_HIP / SA_TRY.
 #pragma once
 #include <stdint.h>
 
@@ -320,17 +322,16 @@ static int match_stats_device(const uint8_t* d_text, uint64_t n, const uint32_t*
 }
 
 // host in, host out (sa_match: off != NULL, nq patterns in buf; sa_matching_stats:
-// off == NULL, nq = the length of the string at buf); every device buffer is
-// freed on every path
+// off == NULL, nq = the length of the string at buf), over the steps of sa_host.h
 static int match_host(const uint8_t* text, uint64_t n, const void* sa, int sa_width, const uint8_t* buf,
                       const uint64_t* off, uint64_t nq, uint64_t max_len, bool sliding, uint64_t* len_out,
                       uint64_t* lo_out, uint64_t* hi_out, uint32_t flags) {
-    if (sa_width != 4 && sa_width != 8) return set_err(SA_E_INVALID, "sa_width must be 4 or 8");
+    SA_TRY(check_width(sa_width));
     if (flags > SA_FIND_WAVE) return set_err(SA_E_INVALID, "flags must be 0, SA_FIND_LANE or SA_FIND_WAVE");
     if (nq == 0) return SA_OK;
     if ((!sliding && !off) || !len_out || (n && (!text || !sa))) return set_err(SA_E_INVALID, "NULL host pointer");
     if (!lo_out != !hi_out) return set_err(SA_E_INVALID, "lo_out and hi_out: both or neither");
-    if (n > 0xFFFFFFFFull) return set_err(SA_E_INVALID, "n too large");
+    SA_TRY(check_n32(n));
     uint64_t buf_bytes = nq;
     if (!sliding) {
         for (uint64_t q = 0; q < nq; ++q)
@@ -339,63 +340,26 @@ static int match_host(const uint8_t* text, uint64_t n, const void* sa, int sa_wi
     }
     if (buf_bytes && !buf) return set_err(SA_E_INVALID, "NULL host pointer");
     std::vector<uint32_t> narrow;
-    const void* src = sa;
-    if (sa_width == 8) {
-        narrow.resize(n);
-        const int64_t* w = (const int64_t*)sa;
-        for (uint64_t i = 0; i < n; ++i) {
-            if (w[i] < 0 || (uint64_t)w[i] >= n) return set_err(SA_E_INVALID, "SA entry out of range");
-            narrow[i] = (uint32_t)w[i];
-        }
-        src = narrow.data();
-    }
-    if (sa_device_count() <= 0) return set_err(SA_E_HIP, "no HIP device visible (libsa_hip needs an MI355X)");
+    const void* src = nullptr;
+    SA_TRY(narrow_sa(sa, n, sa_width, narrow, &src));
+    SA_TRY(need_device());
     const bool bounds = lo_out != nullptr;
-    const int outs = bounds ? 3 : 1;
-    void* d[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // text, sa, buf, off, len | lo | hi
-    const size_t bytes[5] = {(size_t)align_up(n + 1, 256), (size_t)align_up(n + 1, 64) * 4,
-                             (size_t)align_up(buf_bytes + 1, 256), (size_t)(sliding ? 1 : nq + 1) * 8,
-                             (size_t)nq * 4 * outs};
-    int rc = SA_OK;
-    for (int i = 0; i < 5 && rc == SA_OK; ++i)
-        if (hipMalloc(&d[i], bytes[i]) != hipSuccess) {
-            (void)hipGetLastError();
-            rc = set_err(SA_E_NOMEM, "device allocation failed");
-        }
-    std::vector<uint32_t> res;
-    if (rc == SA_OK) {
-        if (copy_h2d(d[0], text, n, nullptr) != SA_OK || copy_h2d(d[1], src, n * 4, nullptr) != SA_OK ||
-            copy_h2d(d[2], buf, buf_bytes, nullptr) != SA_OK ||
-            (!sliding && copy_h2d(d[3], off, (nq + 1) * 8, nullptr) != SA_OK) || host_sync(nullptr) != hipSuccess)
-            rc = set_err(SA_E_HIP, "H2D copy failed: %s", g_err.c_str());
-    }
-    if (rc == SA_OK) {
-        uint32_t* d_len = (uint32_t*)d[4];
-        uint32_t* d_lo = bounds ? d_len + nq : nullptr;
-        uint32_t* d_hi = bounds ? d_len + 2 * nq : nullptr;
-        rc = sliding ? match_stats_device((const uint8_t*)d[0], n, (const uint32_t*)d[1], (const uint8_t*)d[2], nq,
-                                          max_len, d_len, d_lo, d_hi, flags, nullptr)
-                     : match_device((const uint8_t*)d[0], n, (const uint32_t*)d[1], (const uint8_t*)d[2], buf_bytes,
-                                    (const uint64_t*)d[3], nq, d_len, d_lo, d_hi, flags, nullptr);
-    }
-    if (rc == SA_OK) {
-        res.resize((size_t)outs * nq);
-        if (hipMemcpyAsync(res.data(), d[4], (size_t)nq * 4 * outs, hipMemcpyDeviceToHost, nullptr) != hipSuccess ||
-            host_sync(nullptr) != hipSuccess) {
-            rc = set_err(SA_E_HIP, "search or D2H copy failed: %s", hipGetErrorString(hipGetLastError()));
-        }
-    }
-    for (int i = 0; i < 5; ++i)
-        if (d[i]) hipFree(d[i]);
-    if (rc != SA_OK) return rc;
-    for (uint64_t q = 0; q < nq; ++q) {
-        len_out[q] = res[q];
-        if (bounds) {
-            lo_out[q] = res[nq + q];
-            hi_out[q] = res[2 * nq + q];
-        }
-    }
-    return SA_OK;
+    DevBuf d_text, d_sa, d_buf, d_off, d_res;   // d_res: len | lo | hi
+    SA_TRY(d_text.alloc(align_up(n + 1, 256)));
+    SA_TRY(d_sa.alloc(align_up(n + 1, 64) * 4));
+    SA_TRY(d_buf.alloc(align_up(buf_bytes + 1, 256)));
+    SA_TRY(d_off.alloc((sliding ? 1 : nq + 1) * 8));   // the sliding form has no offsets: nothing is uploaded
+    SA_TRY(d_res.alloc(nq * 4 * (bounds ? 3 : 1)));
+    SA_TRY(upload({{d_text.p, text, n}, {d_sa.p, src, n * 4}, {d_buf.p, buf, buf_bytes},
+                   {d_off.p, off, sliding ? 0 : (nq + 1) * 8}}));
+    uint32_t* d_len = d_res.as<uint32_t>();
+    uint32_t* d_lo = bounds ? d_len + nq : nullptr;
+    uint32_t* d_hi = bounds ? d_len + 2 * nq : nullptr;
+    SA_TRY(sliding ? match_stats_device(d_text.as<uint8_t>(), n, d_sa.as<uint32_t>(), d_buf.as<uint8_t>(), nq, max_len,
+                                        d_len, d_lo, d_hi, flags, nullptr)
+                   : match_device(d_text.as<uint8_t>(), n, d_sa.as<uint32_t>(), d_buf.as<uint8_t>(), buf_bytes,
+                                  d_off.as<uint64_t>(), nq, d_len, d_lo, d_hi, flags, nullptr));
+    return download_u64({{len_out, d_len}, {lo_out, d_lo}, {hi_out, d_hi}}, nq);
 }
 
 }  // namespace sa
