@@ -48,6 +48,14 @@ LOCATE_SA_ORDER = 1
 LOCATE_SMALL_CHUNKS = 2
 LOCATE_TILE = 2048
 LOCATE_ORDERS = {"text": 0, "sa": LOCATE_SA_ORDER}
+# sa_mems (include/sa_hip.h SA_MEM_*): the info words ([0] total MEMs, [1]
+# candidates, [2] skipped positions), the positive status of a call stopped by
+# max_candidates, and the flags that force one right-extension path
+MEM_INFO = 3
+MEM_TOO_MANY = 1
+MEM_LANE = 1
+MEM_WAVE = 2
+MEM_MODES = {"auto": 0, "lane": MEM_LANE, "wave": MEM_WAVE}
 
 # every symbol include/*.h declares
 DROPIN_SYMBOLS = ["create_suffix_array", "destroy_suffix_array", "build_suffix_array",
@@ -61,6 +69,7 @@ EXT_SYMBOLS = ["sa_context_create", "sa_context_destroy", "sa_context_set_debug"
                "sa_match_device", "sa_matching_stats_device", "sa_match", "sa_matching_stats",
                "sa_bwt_device", "sa_bwt", "sa_inverse_device", "sa_inverse",
                "sa_locate_device", "sa_locate",
+               "sa_mems_device", "sa_mems",
                "sa_dist_begin", "sa_dist_cuts", "sa_dist_plan_cuts", "sa_dist_reserve", "sa_dist_release", "sa_dist_round1", "sa_dist_req_count", "sa_dist_req_fill",
                "sa_dist_answer", "sa_dist_refine",
                "sa_last_error", "sa_host_syncs", "sa_device_count", "sa_version", "sa_struct_size"]
@@ -276,6 +285,12 @@ def lib() -> ctypes.CDLL:
     L.sa_locate_device.restype = i32
     L.sa_locate.argtypes = [vp, u64, i32, vp, vp, u64, u64, ctypes.c_uint32, vp, vp, u64]
     L.sa_locate.restype = i32
+    L.sa_mems_device.argtypes = [vp, vp, u64, vp, vp, u64, u64, u64, u64, ctypes.c_uint32, vp, vp, vp, u64,
+                                 ctypes.POINTER(u64), vp]
+    L.sa_mems_device.restype = i32
+    L.sa_mems.argtypes = [vp, u64, vp, i32, vp, u64, u64, u64, u64, ctypes.c_uint32, vp, vp, vp, u64,
+                          ctypes.POINTER(u64)]
+    L.sa_mems.restype = i32
     DI =ctypes.POINTER(SaDistInfo)
     L.sa_dist_begin.argtypes = [vp, vp, u64, i32, i32, ctypes.POINTER(ctypes.c_uint32), vp, vp, DI]
     L.sa_dist_cuts.argtypes = [vp, ctypes.POINTER(u64), DI]

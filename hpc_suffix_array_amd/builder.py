@@ -333,6 +333,78 @@ def matching_statistics(text, sa, query, max_len: int = 0, mode: str = "auto", b
     return (out[0], out[1], out[2]) if bounds else out[0]
 
 
+def _mem_mode(mode: str) -> int:
+    """The SA_MEM_* flags of ``mode``."""
+    if mode not in N.MEM_MODES:
+        raise ValueError(f"mode {mode!r}: one of {sorted(N.MEM_MODES)}")
+    return N.MEM_MODES[mode]
+
+
+def _mems_host(t_ptr, n: int, sa_ptr, width: int, query, min_len: int, max_occ: int, max_candidates: int, mode: str,
+               return_info: bool):
+    """sa_mems over host pointers: a sizing call, then the call that fills
+    the arrays; (qpos, tpos, length) as int64, with the info dict on request."""
+    flags = _mem_mode(mode)
+    if min_len < 1:
+        raise ValueError("min_len must be at least 1")
+    if max_occ < 0 or max_candidates < 0:
+        raise ValueError("max_occ and max_candidates: 0 (none) or a positive bound")
+    q = _as_bytes_array(query).reshape(-1)
+    m = int(q.size)
+    off = np.zeros(m + 1, dtype=np.uint64)
+    info = (ctypes.c_uint64 * N.MEM_INFO)()
+    L = N.lib()
+
+    def call(tpos, length, cap):
+        rc = N.check(L.sa_mems(t_ptr if n else None, n, sa_ptr if n else None, width, q.ctypes.data if m else None, m,
+                               int(min_len), int(max_occ), int(max_candidates), flags, off.ctypes.data,
+                               None if tpos is None else tpos.ctypes.data,
+                               None if length is None else length.ctypes.data, cap, info), "sa_mems")
+        if rc == N.MEM_TOO_MANY:
+            raise N.SAError(f"sa_mems: {int(info[1])} candidates are more than max_candidates = {max_candidates} "
+                            f"(raise it, raise min_len, or set max_occ)")
+
+    call(None, None, 0)
+    total = int(info[0])
+    dt = np.int64 if width == 8 else np.uint32
+    tpos, length = np.empty(max(total, 1), dtype=dt), np.empty(max(total, 1), dtype=dt)
+    if total:
+        call(tpos, length, total)
+        if int(info[0]) != total:
+            raise N.SAError(f"sa_mems: {int(info[0])} MEMs after a sizing call that counted {total}")
+    o = off.astype(np.int64)
+    qpos = np.repeat(np.arange(m, dtype=np.int64), np.diff(o))
+    out = (qpos, tpos[:total].astype(np.int64), length[:total].astype(np.int64))
+    if return_info:
+        return out + ({"total": total, "candidates": int(info[1]), "skipped": int(info[2]), "offsets": o},)
+    return out
+
+
+def maximal_exact_matches(text, sa, query, min_len: int, max_occ: int = 0, max_candidates: int = 0,
+                          mode: str = "auto", return_info: bool = False):
+    """Maximal exact matches of ``query`` against ``text`` on the GPU (sa_mems).
+
+    ``sa`` is the suffix array of ``text``.  Returns ``(qpos, tpos, length)``,
+    three int64 arrays sorted by (qpos, tpos): ``query[qpos:qpos + length] ==
+    text[tpos:tpos + length]``, ``length >= min_len``, and the match can be
+    extended neither to the left nor to the right.  Every such triple is
+    listed once.  ``max_occ`` (0: none) drops the matches whose first
+    ``min_len`` bytes occur more than ``max_occ`` times in the text: the
+    repeat filter of seeders, and the bound on the work, which is proportional
+    to the candidates (the seed occurrences of the positions that stay).
+    ``max_candidates`` (0: none) raises SAError, with the candidate count in
+    the message, instead of enumerating more candidates than that.
+    ``mode``: "auto", or "lane" / "wave" to force one right-extension path
+    (tests, A/B runs).  ``return_info=True`` appends a dict: ``total``,
+    ``candidates``, ``skipped`` (positions dropped by ``max_occ``) and
+    ``offsets`` (the CSR offsets over the query positions, len(query) + 1)."""
+    t, s = _text_and_sa(text, sa)
+    _mem_mode(mode)
+    N.require_device()
+    return _mems_host(t.ctypes.data, int(t.size), s.ctypes.data, 8 if s.dtype == np.int64 else 4, query, min_len,
+                      max_occ, max_candidates, mode, return_info)
+
+
 def _bwt_host(t_ptr, n: int, sa_ptr, width: int, stats: bool):
     """sa_bwt over host pointers: (bwt uint8[n], the SA_BWT_STATS words or None)."""
     out = np.empty(max(n, 1), dtype=np.uint8)
@@ -445,6 +517,16 @@ class SuffixArray:
         c = self.p.contents
         out, st = _bwt_host(c.str, self.n, ctypes.cast(c.sa, ctypes.c_void_p).value, 4, True)
         return out.tobytes(), int(st[0])
+
+    def mems(self, query, min_len: int, max_occ: int = 0, max_candidates: int = 0, mode: str = "auto",
+             return_info: bool = False):
+        """(qpos, tpos, length): the maximal exact matches of ``query`` against
+        the text, as maximal_exact_matches gives them (sa_mems at width 4 over
+        the object's own str / sa; build() first)."""
+        N.require_device()
+        c = self.p.contents
+        return _mems_host(c.str, self.n, ctypes.cast(c.sa, ctypes.c_void_p).value, 4, query, min_len, max_occ,
+                          max_candidates, mode, return_info)
 
     def count(self, pattern) -> int:
         lo, hi = self.find(pattern)
@@ -619,6 +701,29 @@ class DeviceBuilder:
                                         None if d_pos is None else self._ptr(d_pos), int(pos_cap),
                                         ctypes.byref(total), s), "sa_locate_device")
         return int(total.value)
+
+    def mems(self, d_text, n: int, d_sa, d_query, m: int, min_len: int, d_off, d_tpos, d_len, out_cap: int,
+             max_occ: int = 0, max_candidates: int = 0, mode: str = "auto", stream=None) -> tuple:
+        """Maximal exact matches of the m bytes at d_query against the text,
+        everything in HBM (sa_mems_device): d_off m + 1 uint64, d_tpos / d_len
+        out_cap uint32 each at any 4-byte alignment.  Returns ``(total,
+        candidates, skipped)``.  The triples are written only when the total
+        fits out_cap and d_tpos / d_len are not None: call once with
+        ``d_tpos=None, d_len=None`` to size the outputs (d_off is filled),
+        allocate, and call again.  Raises SAError when the candidates exceed
+        ``max_candidates``.  Waits for ``stream``."""
+        flags = _mem_mode(mode)
+        s = _stream(stream)
+        info = (ctypes.c_uint64 * N.MEM_INFO)()
+        rc = N.check(self.L.sa_mems_device(self.ctx, self._ptr(d_text), n, self._ptr(d_sa), self._ptr(d_query), m,
+                                           int(min_len), int(max_occ), int(max_candidates), flags, self._ptr(d_off),
+                                           None if d_tpos is None else self._ptr(d_tpos),
+                                           None if d_len is None else self._ptr(d_len), int(out_cap), info, s),
+                     "sa_mems_device")
+        if rc == N.MEM_TOO_MANY:
+            raise N.SAError(f"sa_mems_device: {int(info[1])} candidates are more than max_candidates = "
+                            f"{max_candidates}")
+        return int(info[0]), int(info[1]), int(info[2])
 
     def close(self) -> None:
         if self.ctx:

@@ -2469,6 +2469,10 @@ static int scan_i64(int64_t* d_v, uint64_t m, hipStream_t s) {
 // are summed by scan_i64 above)
 #include "sa_locate.h"
 
+// maximal exact matches of a query: seeds by sa_match.h, their hits by
+// sa_locate.h, the left check, the right extension and the compaction here
+#include "sa_mem.h"
+
 extern "C" {
 
 int sa_running_max_i64_device(int64_t* d_v, uint64_t m, void* stream) {

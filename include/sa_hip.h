@@ -402,6 +402,80 @@ int sa_locate_device(sa_context* ctx, uint64_t n, const uint32_t* d_sa, const ui
 int sa_locate(const void* sa, uint64_t n, int sa_width, const uint64_t* lo, const uint64_t* hi, uint64_t nq,
               uint64_t max_hits, uint32_t flags, uint64_t* off_out /* nq + 1 */, void* pos_out, uint64_t pos_cap);
 
+/* ---- maximal exact matches of a query against the text -------------------
+ * (csrc/sa_mem.h).  Text T of n bytes with its suffix array, query Q of m
+ * bytes, min_len = L >= 1.  A MEM is a triple (i, p, l) with all of:
+ *   Q[i .. i + l) == T[p .. p + l) and l >= L;
+ *   no extension to the right: i + l == m, or p + l == n, or Q[i + l] != T[p + l];
+ *   no extension to the left:  i == 0, or p == 0, or Q[i - 1] != T[p - 1].
+ * Bytes as sa_find has them: binary-safe, 0x00 and 0xFF are ordinary bytes.
+ * The output is every MEM exactly once, ordered by (i, p) ascending, in CSR
+ * form over the query positions: off (m + 1 uint64, off[0] = 0; the MEMs that
+ * start at query position i are entries off[i] .. off[i + 1)), tpos (uint32
+ * text positions) and len (uint32 lengths; l <= min(n, m)).  The total is
+ * off[m].
+ * max_occ (0 = none): a query position whose seed Q[i .. i + L) occurs more
+ * than max_occ times in the text contributes no MEM and is counted as
+ * skipped; that is, a MEM is dropped exactly when its first L bytes occur more
+ * than max_occ times.  This is the one knob that bounds the work: the work is
+ * proportional to the candidates, the sum of the seed occurrences over the
+ * positions that are not skipped.
+ * max_candidates (0 = none): when the candidates exceed it nothing is
+ * enumerated and the call returns SA_MEM_TOO_MANY (a positive status, as
+ * sa_check's) with the info words filled and off all zero.  Temporaries are
+ * about 4 bytes per candidate on top of sa_locate_device's own for that many
+ * hits, plus 20 bytes per query position.
+ * info: SA_MEM_INFO uint64 on the host: [0] the total (0 with
+ * SA_MEM_TOO_MANY), [1] the candidates, [2] the skipped positions.
+ * How it works: seeds by sa_matching_stats_device with max_len = L, their
+ * hits by sa_locate_device (so the candidates are in (i, p) order), then the
+ * MEM list is a stable compaction of the candidate list: a candidate stays
+ * iff it is left-maximal, and each one that stays is extended to the right.
+ * A lane extends by 8-byte words; in auto mode it hands an extension that
+ * passes 512 bytes to a wavefront (512 bytes a step).  DESIGN.md section 14. */
+#define SA_MEM_INFO 3
+#define SA_MEM_TOO_MANY 1
+#define SA_MEM_LANE 1u   /* tests, A/B: every right extension by its own lane */
+#define SA_MEM_WAVE 2u   /* tests, A/B: every right extension by a wavefront */
+
+/* d_text: n bytes, d_sa: n uint32, d_query: m bytes, d_off: m + 1 uint64,
+ * d_tpos / d_len: out_cap uint32 each or both NULL, all in device memory; n
+ * and m <= 2^32 - 1.  d_tpos and d_len are both given or both NULL (one of
+ * them NULL is SA_E_INVALID).  When they are NULL, or when the total exceeds
+ * out_cap, d_off and info are filled, nothing in d_tpos / d_len is touched
+ * and the call returns SA_OK: the sizing call, after which the caller
+ * allocates and calls again.  Exactly [0, total) of d_tpos and d_len and
+ * d_off[0, m] are written; the outputs may have any 4-byte alignment (d_off
+ * 8-byte).
+ * Synchronises `stream`.  Host waits per call: one for the seed counts,
+ * sa_locate_device's own (one; more when a position has more than
+ * SA_LOCATE_TILE hits), and one for the total.  Temporaries are
+ * stream-ordered allocations (SA_E_NOMEM when one fails).
+ * n == 0, m == 0 or L > min(n, m): SA_OK, total 0, off all zero, info zero,
+ * no kernel.  L == 0 is SA_E_INVALID.
+ * Checked before any HIP call (SA_E_INVALID, each with its own message): a
+ * NULL ctx; a NULL d_text or d_sa with n > 0; a NULL d_query with m > 0; a
+ * NULL d_off or info; n or m above 2^32 - 1; unknown flags (or both of them);
+ * an output that is one of the inputs or another output.
+ * Precondition: d_sa is a valid suffix array of the text.  Without it the
+ * results are unspecified, but no load leaves the four input buffers: an SA
+ * entry >= n is clamped to n - 1, p - 1 and p + l never index outside [0, n),
+ * and every extension loop ends at min(n - p, m - i). */
+int sa_mems_device(sa_context* ctx, const uint8_t* d_text, uint64_t n, const uint32_t* d_sa, const uint8_t* d_query,
+                   uint64_t m, uint64_t min_len, uint64_t max_occ, uint64_t max_candidates, uint32_t flags,
+                   uint64_t* d_off /* m + 1 */, uint32_t* d_tpos, uint32_t* d_len, uint64_t out_cap,
+                   uint64_t info[SA_MEM_INFO], void* stream);
+/* Host in, host out: sa, tpos_out and len_out have width sa_width (4 or 8; a
+ * width-8 SA entry outside [0, n) is SA_E_INVALID before any device work).
+ * The total is found first and the device outputs are allocated then, so a
+ * caller may pass out_cap = 0 and NULL outputs to learn the total (info[0])
+ * and off_out, and call again.  The three returns without a kernel above need
+ * no device.  Arguments are checked as the device form checks them. */
+int sa_mems(const uint8_t* text, uint64_t n, const void* sa, int sa_width, const uint8_t* query, uint64_t m,
+            uint64_t min_len, uint64_t max_occ, uint64_t max_candidates, uint32_t flags,
+            uint64_t* off_out /* m + 1 */, void* tpos_out, void* len_out /* width sa_width */, uint64_t out_cap,
+            uint64_t info[SA_MEM_INFO]);
+
 /* ---- building blocks of the range-partitioned multi-GPU build ----------
  * (hpc_suffix_array_amd/distributed.py drives these per rank; the exchange
  * steps between them are RCCL collectives over xGMI.)                      */
