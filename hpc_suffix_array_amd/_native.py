@@ -56,6 +56,12 @@ MEM_TOO_MANY = 1
 MEM_LANE = 1
 MEM_WAVE = 2
 MEM_MODES = {"auto": 0, "lane": MEM_LANE, "wave": MEM_WAVE}
+# sa_lpf / sa_lz77 (include/sa_hip.h SA_LPF_NONE): "no earlier occurrence" in a
+# uint32 SRC array or phrase source (-1 in the int64 arrays of the Python
+# interface); LZ_TILE: the ranks / positions one workgroup handles (csrc/
+# sa_lz.h kLzTile)
+LPF_NONE = 0xFFFFFFFF
+LZ_TILE = 4096
 
 # every symbol include/*.h declares
 DROPIN_SYMBOLS = ["create_suffix_array", "destroy_suffix_array", "build_suffix_array",
@@ -70,6 +76,7 @@ EXT_SYMBOLS = ["sa_context_create", "sa_context_destroy", "sa_context_set_debug"
                "sa_bwt_device", "sa_bwt", "sa_inverse_device", "sa_inverse",
                "sa_locate_device", "sa_locate",
                "sa_mems_device", "sa_mems",
+               "sa_lpf_device", "sa_lpf", "sa_lz77_device", "sa_lz77",
                "sa_dist_begin", "sa_dist_cuts", "sa_dist_plan_cuts", "sa_dist_reserve", "sa_dist_release", "sa_dist_round1", "sa_dist_req_count", "sa_dist_req_fill",
                "sa_dist_answer", "sa_dist_refine",
                "sa_last_error", "sa_host_syncs", "sa_device_count", "sa_version", "sa_struct_size"]
@@ -291,6 +298,14 @@ def lib() -> ctypes.CDLL:
     L.sa_mems.argtypes = [vp, u64, vp, i32, vp, u64, u64, u64, u64, ctypes.c_uint32, vp, vp, vp, u64,
                           ctypes.POINTER(u64)]
     L.sa_mems.restype = i32
+    L.sa_lpf_device.argtypes = [vp, vp, u64, vp, vp, vp, vp, vp]
+    L.sa_lpf_device.restype = i32
+    L.sa_lz77_device.argtypes = [vp, u64, vp, vp, vp, vp, vp, u64, ctypes.POINTER(u64), vp]
+    L.sa_lz77_device.restype = i32
+    L.sa_lpf.argtypes = [vp, u64, vp, i32, vp, vp]
+    L.sa_lpf.restype = i32
+    L.sa_lz77.argtypes = [vp, u64, vp, i32, vp, vp, vp, u64, ctypes.POINTER(u64)]
+    L.sa_lz77.restype = i32
     DI =ctypes.POINTER(SaDistInfo)
     L.sa_dist_begin.argtypes = [vp, vp, u64, i32, i32, ctypes.POINTER(ctypes.c_uint32), vp, vp, DI]
     L.sa_dist_cuts.argtypes = [vp, ctypes.POINTER(u64), DI]

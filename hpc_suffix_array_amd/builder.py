@@ -405,6 +405,114 @@ def maximal_exact_matches(text, sa, query, min_len: int, max_occ: int = 0, max_c
                       max_occ, max_candidates, mode, return_info)
 
 
+def _none_to_minus_one(a: np.ndarray) -> np.ndarray:
+    """uint32 / int64 results as int64, "none" (all ones at either width) as -1."""
+    out = a.astype(np.int64)
+    out[out == N.LPF_NONE] = -1
+    return out
+
+
+def _lpf_host(t_ptr, n: int, sa_ptr, width: int):
+    """sa_lpf over host pointers: (lpf, src) as int64, src -1 where none."""
+    dt = np.int64 if width == 8 else np.uint32
+    lpf, src = np.empty(max(n, 1), dtype=dt), np.empty(max(n, 1), dtype=dt)
+    N.check(N.lib().sa_lpf(t_ptr if n else None, n, sa_ptr if n else None, width, lpf.ctypes.data, src.ctypes.data),
+            "sa_lpf")
+    return lpf[:n].astype(np.int64), _none_to_minus_one(src[:n])
+
+
+def _lz77_host(t_ptr, n: int, sa_ptr, width: int):
+    """sa_lz77 over host pointers, one call (z <= n, so n entries always fit):
+    LPF on the device once, the sizing parse and the writing parse, only z in
+    between.  (pos, length, src) as int64."""
+    dt = np.int64 if width == 8 else np.uint32
+    pos, length, src = (np.empty(max(n, 1), dtype=dt) for _ in range(3))
+    z = ctypes.c_uint64()
+    N.check(N.lib().sa_lz77(t_ptr if n else None, n, sa_ptr if n else None, width, pos.ctypes.data, length.ctypes.data,
+                            src.ctypes.data, n, ctypes.byref(z)), "sa_lz77")
+    k = int(z.value)
+    return pos[:k].astype(np.int64), length[:k].astype(np.int64), _none_to_minus_one(src[:k])
+
+
+def _lz_with_lcp(t: np.ndarray, s: np.ndarray, lcp, parse: bool):
+    """The device forms over torch tensors, for a caller who has the LCP array
+    already: the text is not uploaded and the LCP is not computed again."""
+    import torch
+    n = int(t.size)
+    l = np.ascontiguousarray(lcp)
+    if l.size != n:
+        raise ValueError(f"LCP has {l.size} entries for a text of {n} bytes")
+    if n and (int(s.min()) < 0 or int(s.max()) >= n):
+        raise N.SAError("SA entry out of range")
+    if n and (int(l.min()) < 0 or int(l.max()) > n):
+        raise N.SAError("LCP entry out of range")
+    if n == 0:
+        e = np.zeros(0, dtype=np.int64)
+        return (e, e.copy(), e.copy()) if parse else (e, e.copy())
+    dev = torch.device("cuda", 0)
+
+    def up(a):
+        return torch.from_numpy(a.astype(np.uint32).view(np.int32)).to(dev)
+
+    def down(x, k):
+        return x[:k].cpu().numpy().view(np.uint32)
+
+    d_sa, d_lcp = up(s), up(l)
+    d_lpf, d_src = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
+    db = DeviceBuilder(n)
+    try:
+        torch.cuda.synchronize()
+        db.lpf(None, n, d_sa, d_lcp, d_lpf, d_src)
+        if not parse:
+            torch.cuda.synchronize()
+            return down(d_lpf, n).astype(np.int64), _none_to_minus_one(down(d_src, n))
+        z = db.lz77(n, d_lpf, d_src, None, None, None, 0)
+        d_out = [torch.empty(max(z, 1), dtype=torch.int32, device=dev) for _ in range(3)]
+        if db.lz77(n, d_lpf, d_src, d_out[0], d_out[1], d_out[2], z) != z:
+            raise N.SAError(f"sa_lz77_device: the phrase count changed after a sizing call that counted {z}")
+        return (down(d_out[0], z).astype(np.int64), down(d_out[1], z).astype(np.int64),
+                _none_to_minus_one(down(d_out[2], z)))
+    finally:
+        db.close()
+
+
+def longest_previous_factor(text, sa, lcp=None):
+    """Longest previous factor array of ``text`` on the GPU (sa_lpf).
+
+    ``sa`` is the suffix array of ``text``.  Returns ``(lpf, src)``, two int64
+    arrays in text order: ``lpf[i]`` is the length of the longest prefix of
+    ``text[i:]`` that also starts at some ``j < i`` (the two occurrences may
+    overlap), and ``src[i]`` is the canonical such ``j`` of include/sa_hip.h,
+    -1 where ``lpf[i] == 0``.  No text is compared: the lengths are LCP range
+    minima, so a highly repetitive text costs what its length costs.  ``lcp``:
+    the LCP array of ``sa`` as lcp_array gives it, when the caller has it; the
+    device forms then run on it and the LCP is not computed again."""
+    t, s = _text_and_sa(text, sa)
+    N.require_device()
+    if lcp is not None:
+        return _lz_with_lcp(t, s, lcp, False)
+    return _lpf_host(t.ctypes.data, int(t.size), s.ctypes.data, 8 if s.dtype == np.int64 else 4)
+
+
+def lz77_factorize(text, sa, lcp=None):
+    """Greedy, self-referential LZ77 factorisation of ``text`` on the GPU
+    (sa_lz77).
+
+    Returns ``(pos, length, src)``, three int64 arrays with one entry per
+    phrase in text order: the phrases tile the text (``pos[0] == 0``,
+    ``pos[k + 1] == pos[k] + length[k]``), ``text[pos:pos + length]`` is the
+    longest prefix of ``text[pos:]`` that occurs earlier, copied from ``src``
+    (the copy may run into the phrase itself), and a literal has ``length == 1``
+    and ``src == -1``.  ``len(pos)`` is z, the number of phrases.  LPF is
+    computed on the device once and parsed there; only z comes back in
+    between.  ``lcp`` as for longest_previous_factor."""
+    t, s = _text_and_sa(text, sa)
+    N.require_device()
+    if lcp is not None:
+        return _lz_with_lcp(t, s, lcp, True)
+    return _lz77_host(t.ctypes.data, int(t.size), s.ctypes.data, 8 if s.dtype == np.int64 else 4)
+
+
 def _bwt_host(t_ptr, n: int, sa_ptr, width: int, stats: bool):
     """sa_bwt over host pointers: (bwt uint8[n], the SA_BWT_STATS words or None)."""
     out = np.empty(max(n, 1), dtype=np.uint8)
@@ -528,6 +636,22 @@ class SuffixArray:
         return _mems_host(c.str, self.n, ctypes.cast(c.sa, ctypes.c_void_p).value, 4, query, min_len, max_occ,
                           max_candidates, mode, return_info)
 
+    def lpf(self) -> tuple:
+        """(lpf, src): the longest previous factor array of the text and its
+        canonical sources, as longest_previous_factor gives them (sa_lpf at
+        width 4 over the object's own str / sa; build() first)."""
+        N.require_device()
+        c = self.p.contents
+        return _lpf_host(c.str, self.n, ctypes.cast(c.sa, ctypes.c_void_p).value, 4)
+
+    def lz77(self) -> tuple:
+        """(pos, length, src): the LZ77 factorisation of the text, as
+        lz77_factorize gives it (sa_lz77 at width 4 over the object's own str
+        / sa; build() first)."""
+        N.require_device()
+        c = self.p.contents
+        return _lz77_host(c.str, self.n, ctypes.cast(c.sa, ctypes.c_void_p).value, 4)
+
     def count(self, pattern) -> int:
         lo, hi = self.find(pattern)
         return hi - lo
@@ -585,6 +709,11 @@ class DeviceBuilder:
     @staticmethod
     def _ptr(x) -> int:
         return x if isinstance(x, int) else int(x.data_ptr())
+
+    @classmethod
+    def _opt(cls, x):
+        """A pointer that may be absent (None: NULL)."""
+        return None if x is None else cls._ptr(x)
 
     def build(self, d_text, n: int, d_sa, stream=None, profile: bool = False, schedule: str = "packed",
               init_chars: int = 0, radix: str = "onesweep", round1: str = "auto", debug=(), span_extra: int = 0,
@@ -724,6 +853,33 @@ class DeviceBuilder:
             raise N.SAError(f"sa_mems_device: {int(info[1])} candidates are more than max_candidates = "
                             f"{max_candidates}")
         return int(info[0]), int(info[1]), int(info[2])
+
+    def lpf(self, d_text, n: int, d_sa, d_lcp, d_lpf, d_src, stream=None) -> None:
+        """Longest previous factor array and its canonical sources into the n
+        uint32 at d_lpf and d_src (text order, any 4-byte alignment; "none" is
+        N.LPF_NONE), everything in HBM (sa_lpf_device).  With ``d_lcp`` (the
+        LCP array of d_sa, n uint32) the text is not read and ``d_text`` may be
+        None: the call is then only enqueued on ``stream``.  ``d_lcp=None``
+        computes the LCP array first, as lcp does."""
+        s = _stream(stream)
+        o = self._opt
+        N.check(self.L.sa_lpf_device(self.ctx, o(d_text), n, o(d_sa), o(d_lcp), o(d_lpf), o(d_src), s),
+                "sa_lpf_device")
+
+    def lz77(self, n: int, d_lpf, d_src, d_pos, d_len, d_fsrc, out_cap: int, stream=None) -> int:
+        """Greedy LZ77 parse of the LPF / SRC arrays lpf wrote, everything in
+        HBM (sa_lz77_device): phrase k is (d_pos[k], d_len[k], d_fsrc[k]),
+        out_cap uint32 each at any 4-byte alignment, a literal with length 1
+        and source N.LPF_NONE.  Returns z, the number of phrases.  The phrases
+        are written only when z fits out_cap and the three outputs are not
+        None: call once with ``None, None, None, 0`` to size them, allocate,
+        and call again.  Waits for ``stream``."""
+        s = _stream(stream)
+        z = ctypes.c_uint64()
+        o = self._opt
+        N.check(self.L.sa_lz77_device(self.ctx, n, o(d_lpf), o(d_src), o(d_pos), o(d_len), o(d_fsrc), int(out_cap),
+                                      ctypes.byref(z), s), "sa_lz77_device")
+        return int(z.value)
 
     def close(self) -> None:
         if self.ctx:

@@ -2473,6 +2473,10 @@ static int scan_i64(int64_t* d_v, uint64_t m, hipStream_t s) {
 // sa_locate.h, the left check, the right extension and the compaction here
 #include "sa_mem.h"
 
+// the longest previous factor array (nearest smaller values over the SA with
+// LCP range minima) and the LZ77 factorisation parsed from it
+#include "sa_lz.h"
+
 extern "C" {
 
 int sa_running_max_i64_device(int64_t* d_v, uint64_t m, void* stream) {

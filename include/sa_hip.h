@@ -476,6 +476,76 @@ int sa_mems(const uint8_t* text, uint64_t n, const void* sa, int sa_width, const
             uint64_t* off_out /* m + 1 */, void* tpos_out, void* len_out /* width sa_width */, uint64_t out_cap,
             uint64_t info[SA_MEM_INFO]);
 
+/* ---- longest previous factor and LZ77 factorisation ----------------------
+ * (csrc/sa_lz.h).  Text T of n bytes (n <= 2^32 - 1), its suffix array SA and
+ * LCP as sa_lcp_device defines it (lcp[0] = 0, lcp[r] = lcp(SA[r - 1],
+ * SA[r])).  Bytes are binary-safe; the end of the string sorts smallest.
+ * LPF[i] = max { l : some j < i has T[j .. j + l) == T[i .. i + l) }; the
+ * earlier occurrence may overlap position i; LPF[0] = 0.
+ * SRC[i], canonical (so two calls agree bit for bit): with r the rank of
+ * suffix i, a the largest rank < r with SA[a] < i and b the smallest rank > r
+ * with SA[b] < i (either may be absent), la = min lcp(a + 1 .. r] and lb =
+ * min lcp(r + 1 .. b] (0 for an absent side): LPF[i] = max(la, lb); SRC[i] =
+ * SA[a] when la >= lb and la > 0, else SA[b] when lb > 0, else SA_LPF_NONE,
+ * which can never be a position.
+ * LZ77, greedy and self-referential: phrase starts p0 = 0, p(k+1) = p(k) +
+ * max(1, LPF[p(k)]) until n is reached; phrase k is (pos = p(k), len = max(1,
+ * LPF[p(k)]), src = SRC[p(k)]).  A literal has len 1 and src SA_LPF_NONE; its
+ * byte is T[pos].  z is the number of phrases, emitted in text order.
+ * The cost does not depend on the lengths: they are LCP range minima gathered
+ * during the nearest-smaller search, the text is never compared.  DESIGN.md
+ * section 15. */
+#define SA_LPF_NONE 0xFFFFFFFFu
+
+/* d_sa, d_lcp: n uint32; d_lpf, d_src: n uint32 each, in text order, at any
+ * 4-byte alignment (they are written by 4-byte scatters); all in device
+ * memory.  With d_lcp given the text is not read and d_text may be NULL; with
+ * d_lcp == NULL the LCP array is computed by sa_lcp_device's path into a
+ * stream-ordered temporary (d_text: n bytes).
+ * Enqueued on `stream`.  Host waits per call: none with d_lcp given (the call
+ * does not wait for the stream); sa_lcp_device's own without.  Temporaries
+ * are stream-ordered allocations (n / 8 bytes, plus 4 n for the LCP array;
+ * SA_E_NOMEM when one fails).
+ * n == 0: SA_OK, no kernel.  n == 1: LPF = [0], SRC = [SA_LPF_NONE].
+ * Checked before any HIP call (SA_E_INVALID, each with its own message): a
+ * NULL ctx; n above 2^32 - 1; with n > 0 a NULL d_sa, d_lpf or d_src, d_text
+ * and d_lcp both NULL, an output that is not 4-byte aligned, an output that
+ * is one of the inputs or the other output.
+ * Precondition: d_sa is the text's suffix array and d_lcp its LCP array.
+ * Without it the results are unspecified, but no load or store leaves the
+ * buffers: an SA entry >= n is clamped to n - 1 and every walk ends at rank 0
+ * or n - 1. */
+int sa_lpf_device(sa_context* ctx, const uint8_t* d_text, uint64_t n, const uint32_t* d_sa,
+                  const uint32_t* d_lcp /* may be NULL */, uint32_t* d_lpf, uint32_t* d_src, void* stream);
+/* The parse.  d_lpf, d_src: n uint32 as sa_lpf_device writes them; d_pos,
+ * d_len, d_fsrc: out_cap uint32 each at any 4-byte alignment, all three given
+ * or all three NULL.  Neither the text nor the SA is needed.  With NULL
+ * outputs, or when z exceeds out_cap, only *z is filled and nothing else is
+ * touched: the sizing call, after which the caller allocates and calls again.
+ * Exactly [0, z) of each output is written.
+ * Synchronises `stream`.  Host waits per call: three (the candidate count,
+ * the candidate list, z).  Temporaries are stream-ordered allocations (about
+ * 5.2 n bytes; SA_E_NOMEM when one fails).
+ * n == 0: SA_OK, z = 0, no kernel.
+ * next(i) = i + max(1, LPF[i]) is computed in 64 bits and clamped to n, so an
+ * arbitrary d_lpf terminates and stays inside the buffers; its results are
+ * unspecified.
+ * Checked before any HIP call (SA_E_INVALID, each with its own message): a
+ * NULL ctx or z; n above 2^32 - 1; outputs of which only some are NULL; with
+ * n > 0 a NULL d_lpf or d_src, an output that is not 4-byte aligned, an output
+ * that is one of the inputs or another output. */
+int sa_lz77_device(sa_context* ctx, uint64_t n, const uint32_t* d_lpf, const uint32_t* d_src, uint32_t* d_pos,
+                   uint32_t* d_len, uint32_t* d_fsrc, uint64_t out_cap, uint64_t* z, void* stream);
+/* Host in, host out: sa and the outputs have width sa_width (4 or 8; a
+ * width-8 SA entry outside [0, n) is SA_E_INVALID before any device work, and
+ * an SA that is not the text's is SA_E_INVALID).  "None" is all ones at
+ * either width (-1 as int64).  sa_lz77 computes LPF on the device once, finds
+ * z, and writes the phrases when the outputs are given and z <= out_cap; so
+ * out_cap = 0 with NULL outputs is the sizing call.  n == 0 needs no device. */
+int sa_lpf(const uint8_t* text, uint64_t n, const void* sa, int sa_width, void* lpf_out, void* src_out);
+int sa_lz77(const uint8_t* text, uint64_t n, const void* sa, int sa_width, void* pos_out, void* len_out, void* src_out,
+            uint64_t out_cap, uint64_t* z);
+
 /* ---- building blocks of the range-partitioned multi-GPU build ----------
  * (hpc_suffix_array_amd/distributed.py drives these per rank; the exchange
  * steps between them are RCCL collectives over xGMI.)                      */
