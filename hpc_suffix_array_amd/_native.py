@@ -62,6 +62,14 @@ MEM_MODES = {"auto": 0, "lane": MEM_LANE, "wave": MEM_WAVE}
 # sa_lz.h kLzTile)
 LPF_NONE = 0xFFFFFFFF
 LZ_TILE = 4096
+# sa_repeats (include/sa_hip.h SA_REP_*): the kinds, nested (supermaximal within
+# maximal within right-maximal), and the info words ([0] repeats listed, [1]
+# the sum of hi - lo over them, the pos_cap of sa_locate_device)
+REP_RIGHT = 0
+REP_MAXIMAL = 1
+REP_SUPERMAXIMAL = 2
+REP_KINDS = {"right": REP_RIGHT, "maximal": REP_MAXIMAL, "supermaximal": REP_SUPERMAXIMAL}
+REP_INFO = 2
 
 # every symbol include/*.h declares
 DROPIN_SYMBOLS = ["create_suffix_array", "destroy_suffix_array", "build_suffix_array",
@@ -77,6 +85,7 @@ EXT_SYMBOLS = ["sa_context_create", "sa_context_destroy", "sa_context_set_debug"
                "sa_locate_device", "sa_locate",
                "sa_mems_device", "sa_mems",
                "sa_lpf_device", "sa_lpf", "sa_lz77_device", "sa_lz77",
+               "sa_repeats_device", "sa_repeats",
                "sa_dist_begin", "sa_dist_cuts", "sa_dist_plan_cuts", "sa_dist_reserve", "sa_dist_release", "sa_dist_round1", "sa_dist_req_count", "sa_dist_req_fill",
                "sa_dist_answer", "sa_dist_refine",
                "sa_last_error", "sa_host_syncs", "sa_device_count", "sa_version", "sa_struct_size"]
@@ -306,6 +315,11 @@ def lib() -> ctypes.CDLL:
     L.sa_lpf.restype = i32
     L.sa_lz77.argtypes = [vp, u64, vp, i32, vp, vp, vp, u64, ctypes.POINTER(u64)]
     L.sa_lz77.restype = i32
+    L.sa_repeats_device.argtypes = [vp, vp, u64, vp, vp, u64, u64, ctypes.c_uint32, vp, vp, vp, u64,
+                                    ctypes.POINTER(u64), vp]
+    L.sa_repeats_device.restype = i32
+    L.sa_repeats.argtypes = [vp, u64, vp, i32, u64, u64, ctypes.c_uint32, vp, vp, vp, u64, ctypes.POINTER(u64)]
+    L.sa_repeats.restype = i32
     DI =ctypes.POINTER(SaDistInfo)
     L.sa_dist_begin.argtypes = [vp, vp, u64, i32, i32, ctypes.POINTER(ctypes.c_uint32), vp, vp, DI]
     L.sa_dist_cuts.argtypes = [vp, ctypes.POINTER(u64), DI]

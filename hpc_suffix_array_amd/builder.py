@@ -513,6 +513,94 @@ def lz77_factorize(text, sa, lcp=None):
     return _lz77_host(t.ctypes.data, int(t.size), s.ctypes.data, 8 if s.dtype == np.int64 else 4)
 
 
+def _rep_kind(kind: str) -> int:
+    if kind not in N.REP_KINDS:
+        raise ValueError(f"unknown kind {kind!r} (one of {sorted(N.REP_KINDS)})")
+    return N.REP_KINDS[kind]
+
+
+def _rep_filters(min_len: int, min_occ: int):
+    if int(min_len) < 0 or int(min_occ) < 0:
+        raise ValueError("min_len and min_occ must not be negative")
+    return int(min_len), int(min_occ)
+
+
+def _repeats_host(t_ptr, n: int, sa_ptr, width: int, min_len: int, min_occ: int, kind: int):
+    """sa_repeats over host pointers, one call (a text has fewer than n
+    repeats, so n entries always fit): (length, lo, hi) as int64."""
+    min_len, min_occ = _rep_filters(min_len, min_occ)
+    dt = np.int64 if width == 8 else np.uint32
+    length, lo, hi = (np.empty(max(n, 1), dtype=dt) for _ in range(3))
+    info = (ctypes.c_uint64 * N.REP_INFO)()
+    N.check(N.lib().sa_repeats(t_ptr if n else None, n, sa_ptr if n else None, width, min_len, min_occ, kind,
+                               length.ctypes.data, lo.ctypes.data, hi.ctypes.data, n, info), "sa_repeats")
+    k = int(info[0])
+    return length[:k].astype(np.int64), lo[:k].astype(np.int64), hi[:k].astype(np.int64)
+
+
+def _repeats_with_lcp(t: np.ndarray, s: np.ndarray, lcp, min_len: int, min_occ: int, kind: str):
+    """The device form over torch tensors, for a caller who has the LCP array
+    already: the sizing call, then the writing call into outputs of that size."""
+    import torch
+    min_len, min_occ = _rep_filters(min_len, min_occ)
+    n = int(t.size)
+    l = np.ascontiguousarray(lcp)
+    if l.size != n:
+        raise ValueError(f"LCP has {l.size} entries for a text of {n} bytes")
+    if n and (int(s.min()) < 0 or int(s.max()) >= n):
+        raise N.SAError("SA entry out of range")
+    if n and (int(l.min()) < 0 or int(l.max()) > n):
+        raise N.SAError("LCP entry out of range")
+    if n <= 1:
+        e = np.zeros(0, dtype=np.int64)
+        return e, e.copy(), e.copy()
+    dev = torch.device("cuda", 0)
+
+    def up(a):
+        return torch.from_numpy(a.astype(np.uint32).view(np.int32)).to(dev)
+
+    def down(x, k):
+        return x[:k].cpu().numpy().view(np.uint32).astype(np.int64)
+
+    d_text, d_sa, d_lcp = torch.from_numpy(t.copy()).to(dev), up(s), up(l)
+    db = DeviceBuilder(n)
+    try:
+        torch.cuda.synchronize()
+        count, _ = db.repeats(d_text, n, d_sa, d_lcp, min_len, min_occ, kind, None, None, None, 0)
+        d_out = [torch.empty(max(count, 1), dtype=torch.int32, device=dev) for _ in range(3)]
+        if db.repeats(d_text, n, d_sa, d_lcp, min_len, min_occ, kind, d_out[0], d_out[1], d_out[2], count)[0] != count:
+            raise N.SAError(f"sa_repeats_device: the count changed after a sizing call that counted {count}")
+        return down(d_out[0], count), down(d_out[1], count), down(d_out[2], count)
+    finally:
+        db.close()
+
+
+def maximal_repeats(text, sa, min_len: int = 1, min_occ: int = 2, kind: str = "maximal", lcp=None):
+    """The repeats of ``text`` on the GPU (sa_repeats), as SA intervals.
+
+    ``sa`` is the suffix array of ``text``.  Returns ``(length, lo, hi)``,
+    three int64 arrays with one entry per repeat: the string
+    ``text[sa[lo]:sa[lo] + length]`` occurs exactly at ``sa[lo:hi]``, at least
+    twice, and its occurrences are not all followed by the same byte
+    (right-maximal).  ``kind``: ``"right"`` lists every such repeat (the LCP
+    intervals: the internal nodes of the suffix tree), ``"maximal"`` those
+    whose occurrences are not all preceded by the same byte either,
+    ``"supermaximal"`` the maximal repeats that are no proper substring of
+    another maximal repeat.  ``min_len`` and ``min_occ`` filter by length and
+    by ``hi - lo``.  The order is that of the repeats' heads (include/
+    sa_hip.h), so two calls agree exactly; ``locate_intervals(sa, lo, hi)``
+    gives every occurrence.  ``lcp``: the LCP array of ``sa`` as lcp_array
+    gives it, when the caller has it; the device form then runs on it and the
+    LCP is not computed again."""
+    t, s = _text_and_sa(text, sa)
+    k = _rep_kind(kind)
+    _rep_filters(min_len, min_occ)
+    N.require_device()
+    if lcp is not None:
+        return _repeats_with_lcp(t, s, lcp, min_len, min_occ, kind)
+    return _repeats_host(t.ctypes.data, int(t.size), s.ctypes.data, 8 if s.dtype == np.int64 else 4, min_len, min_occ, k)
+
+
 def _bwt_host(t_ptr, n: int, sa_ptr, width: int, stats: bool):
     """sa_bwt over host pointers: (bwt uint8[n], the SA_BWT_STATS words or None)."""
     out = np.empty(max(n, 1), dtype=np.uint8)
@@ -651,6 +739,15 @@ class SuffixArray:
         N.require_device()
         c = self.p.contents
         return _lz77_host(c.str, self.n, ctypes.cast(c.sa, ctypes.c_void_p).value, 4)
+
+    def repeats(self, min_len: int = 1, min_occ: int = 2, kind: str = "maximal") -> tuple:
+        """(length, lo, hi): the repeats of the text as SA intervals, as
+        maximal_repeats gives them (sa_repeats at width 4 over the object's
+        own str / sa; build() first)."""
+        k = _rep_kind(kind)
+        N.require_device()
+        c = self.p.contents
+        return _repeats_host(c.str, self.n, ctypes.cast(c.sa, ctypes.c_void_p).value, 4, min_len, min_occ, k)
 
     def count(self, pattern) -> int:
         lo, hi = self.find(pattern)
@@ -880,6 +977,28 @@ class DeviceBuilder:
         N.check(self.L.sa_lz77_device(self.ctx, n, o(d_lpf), o(d_src), o(d_pos), o(d_len), o(d_fsrc), int(out_cap),
                                       ctypes.byref(z), s), "sa_lz77_device")
         return int(z.value)
+
+    def repeats(self, d_text, n: int, d_sa, d_lcp, min_len: int, min_occ: int, kind: str, d_len, d_lo, d_hi,
+                out_cap: int, stream=None) -> tuple:
+        """The repeats of the text as SA intervals, everything in HBM
+        (sa_repeats_device): repeat k has length d_len[k] and occurs exactly at
+        d_sa[d_lo[k] .. d_hi[k]), out_cap uint32 each at any 4-byte alignment,
+        in the order of their heads.  ``kind``: "right" (every right-maximal
+        repeat; with ``d_lcp`` neither the text nor the SA is read and both may
+        be None), "maximal" or "supermaximal".  ``d_lcp=None`` computes the LCP
+        array first, as lcp does.  Returns ``(count, total_occ)``: the repeats
+        and the sum of hi - lo over them, which is locate's pos_cap for
+        ``locate(n, d_sa, d_lo, d_hi, count, ...)``.  They are written only
+        when count fits out_cap and the three outputs are not None: call once
+        with ``None, None, None, 0`` to size them, allocate, and call again.
+        Waits for ``stream``."""
+        s = _stream(stream)
+        info = (ctypes.c_uint64 * N.REP_INFO)()
+        o = self._opt
+        N.check(self.L.sa_repeats_device(self.ctx, o(d_text), n, o(d_sa), o(d_lcp), int(min_len), int(min_occ),
+                                         _rep_kind(kind), o(d_len), o(d_lo), o(d_hi), int(out_cap), info, s),
+                "sa_repeats_device")
+        return int(info[0]), int(info[1])
 
     def close(self) -> None:
         if self.ctx:

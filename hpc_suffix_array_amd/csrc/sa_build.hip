@@ -2477,6 +2477,11 @@ static int scan_i64(int64_t* d_v, uint64_t m, hipStream_t s) {
 // LCP range minima) and the LZ77 factorisation parsed from it
 #include "sa_lz.h"
 
+// the repeats of the text as LCP intervals (right-maximal, maximal,
+// supermaximal): nearest smaller values over the LCP array, sa_lz.h's walk
+// with the comparison as a parameter
+#include "sa_repeats.h"
+
 extern "C" {
 
 int sa_running_max_i64_device(int64_t* d_v, uint64_t m, void* stream) {

@@ -546,6 +546,75 @@ int sa_lpf(const uint8_t* text, uint64_t n, const void* sa, int sa_width, void* 
 int sa_lz77(const uint8_t* text, uint64_t n, const void* sa, int sa_width, void* pos_out, void* len_out, void* src_out,
             uint64_t out_cap, uint64_t* z);
 
+/* ---- repeats: right-maximal, maximal and supermaximal ---------------------
+ * (csrc/sa_repeats.h).  Text T of n bytes (n <= 2^32 - 1), its suffix array SA
+ * and LCP as sa_lcp_device defines it (lcp[0] = 0, lcp[r] = lcp(SA[r - 1],
+ * SA[r])); lcp[n] reads as 0.  Intervals are half-open.
+ * A repeat is (len, lo, hi) with len >= 1 and hi - lo >= 2: lcp[lo] < len,
+ * lcp[k] >= len for lo < k < hi with equality for some k, lcp[hi] < len.  Its
+ * string T[SA[lo] .. SA[lo] + len) occurs exactly at SA[lo .. hi) and is
+ * right-maximal: its occurrences are not all followed by the same byte (the
+ * end of the text is a follower of its own).  These are the LCP intervals,
+ * the internal nodes of the suffix tree other than the root.  The head of a
+ * repeat is the smallest k in (lo, hi) with lcp[k] == len; a rank is the head
+ * of at most one repeat.  prev(k) = T[SA[k] - 1], and a 257th symbol that
+ * differs from every byte when SA[k] == 0.
+ *   SA_REP_RIGHT         every repeat.
+ *   SA_REP_MAXIMAL       those that are left-maximal too: prev(k), lo <= k <
+ *                        hi, are not all equal.
+ *   SA_REP_SUPERMAXIMAL  lcp[k] == len for all lo < k < hi and the prev(k),
+ *                        lo <= k < hi, are pairwise distinct (so hi - lo <=
+ *                        257): a maximal repeat that is no proper substring
+ *                        of another maximal repeat.
+ * Filters: len >= min_len (0 reads as 1) and hi - lo >= min_occ (0 and 1 read
+ * as 2).  Order: ascending head, so two calls agree bit for bit.
+ * info[0] = the number of repeats listed, info[1] = the sum of hi - lo over
+ * them (the pos_cap of sa_locate_device for all their occurrences: d_lo and
+ * d_hi are what it takes).  DESIGN.md section 16. */
+#define SA_REP_RIGHT 0
+#define SA_REP_MAXIMAL 1
+#define SA_REP_SUPERMAXIMAL 2
+#define SA_REP_INFO 2
+
+/* d_sa, d_lcp: n uint32; d_len, d_lo, d_hi: out_cap uint32 each at any 4-byte
+ * alignment, all three given or all three NULL; all in device memory.  With
+ * NULL outputs, or when info[0] exceeds out_cap, only info is filled and
+ * nothing else is touched: the sizing call, after which the caller allocates
+ * and calls again.  Otherwise exactly [0, info[0]) of each output is written.
+ * SA_REP_RIGHT with d_lcp given reads neither the text nor the SA: d_text and
+ * d_sa may be NULL.  With d_lcp == NULL the LCP array is computed by
+ * sa_lcp_device's path into a stream-ordered temporary.
+ * Synchronises `stream`.  Host waits per call: one with d_lcp given (info,
+ * after everything is enqueued; the writing kernel reads the count on the
+ * device); sa_lcp_device's own and that one without.  Temporaries are
+ * stream-ordered allocations (about 0.38 n bytes for SA_REP_MAXIMAL, 0.19 n
+ * for the other kinds, plus 4 n for the LCP array; SA_E_NOMEM when one fails).
+ * n <= 1: SA_OK, info = {0, 0}, no kernel.
+ * Checked before any HIP call (SA_E_INVALID, each with its own message): a
+ * NULL ctx or info; n above 2^32 - 1; an unknown kind; outputs of which only
+ * some are NULL; with n > 1 a NULL d_text or d_sa where the kind or a NULL
+ * d_lcp needs it, an output that is not 4-byte aligned, an output that is one
+ * of the inputs or another output.
+ * Precondition: d_sa is the text's suffix array and d_lcp its LCP array.
+ * With an arbitrary d_sa or d_lcp given the results are unspecified, but no
+ * load or store leaves the buffers and info[0] <= out_cap holds for what is
+ * written: an SA entry >= n is clamped for the text gather, every walk ends
+ * at rank 0 or n, the supermaximal scan stops after 257 ranks. */
+int sa_repeats_device(sa_context* ctx, const uint8_t* d_text, uint64_t n, const uint32_t* d_sa,
+                      const uint32_t* d_lcp /* may be NULL */, uint64_t min_len, uint64_t min_occ, uint32_t kind,
+                      uint32_t* d_len, uint32_t* d_lo, uint32_t* d_hi, uint64_t out_cap, uint64_t info[SA_REP_INFO],
+                      void* stream);
+/* Host in, host out: sa and the outputs have width sa_width (4 or 8; a
+ * width-8 SA entry outside [0, n) is SA_E_INVALID before any device work, and
+ * an SA that is not the text's is SA_E_INVALID: it is checked against the text
+ * first).  One device computation: the repeats are written into device
+ * buffers of min(out_cap, n) entries and copied out when the outputs are
+ * given and info[0] <= out_cap; out_cap = 0 with NULL outputs is the sizing
+ * call.  n <= 1 needs no device. */
+int sa_repeats(const uint8_t* text, uint64_t n, const void* sa, int sa_width, uint64_t min_len, uint64_t min_occ,
+               uint32_t kind, void* len_out, void* lo_out, void* hi_out /* width sa_width */, uint64_t out_cap,
+               uint64_t info[SA_REP_INFO]);
+
 /* ---- building blocks of the range-partitioned multi-GPU build ----------
  * (hpc_suffix_array_amd/distributed.py drives these per rank; the exchange
  * steps between them are RCCL collectives over xGMI.)                      */
