@@ -70,6 +70,16 @@ REP_MAXIMAL = 1
 REP_SUPERMAXIMAL = 2
 REP_KINDS = {"right": REP_RIGHT, "maximal": REP_MAXIMAL, "supermaximal": REP_SUPERMAXIMAL}
 REP_INFO = 2
+# sa_ibwt (include/sa_hip.h SA_IBWT_INFO): the info words ([0] splitters, [1]
+# the longest stretch of the chain between two splitters, [2] the steps from
+# LF[primary] until the primary row); LF_TILE: the ranks per row of the LF
+# count table; IBWT_S: one rank in IBWT_S is a splitter; IBWT_TILE: the ranks
+# one workgroup's splitters come from (csrc/sa_ibwt.h kLfTile, kIbwtSplitBits,
+# kIbwtTile)
+IBWT_INFO = 3
+LF_TILE = 32768
+IBWT_S = 64
+IBWT_TILE = 16384
 
 # every symbol include/*.h declares
 DROPIN_SYMBOLS = ["create_suffix_array", "destroy_suffix_array", "build_suffix_array",
@@ -86,6 +96,7 @@ EXT_SYMBOLS = ["sa_context_create", "sa_context_destroy", "sa_context_set_debug"
                "sa_mems_device", "sa_mems",
                "sa_lpf_device", "sa_lpf", "sa_lz77_device", "sa_lz77",
                "sa_repeats_device", "sa_repeats",
+               "sa_lf_device", "sa_ibwt_device", "sa_lf", "sa_ibwt", "sa_ibwt_ex",
                "sa_dist_begin", "sa_dist_cuts", "sa_dist_plan_cuts", "sa_dist_reserve", "sa_dist_release", "sa_dist_round1", "sa_dist_req_count", "sa_dist_req_fill",
                "sa_dist_answer", "sa_dist_refine",
                "sa_last_error", "sa_host_syncs", "sa_device_count", "sa_version", "sa_struct_size"]
@@ -320,6 +331,16 @@ def lib() -> ctypes.CDLL:
     L.sa_repeats_device.restype = i32
     L.sa_repeats.argtypes = [vp, u64, vp, i32, u64, u64, ctypes.c_uint32, vp, vp, vp, u64, ctypes.POINTER(u64)]
     L.sa_repeats.restype = i32
+    L.sa_lf_device.argtypes = [vp, vp, u64, u64, vp, vp]
+    L.sa_lf_device.restype = i32
+    L.sa_ibwt_device.argtypes = [vp, vp, u64, u64, vp, vp, ctypes.POINTER(u64), vp]
+    L.sa_ibwt_device.restype = i32
+    L.sa_lf.argtypes = [vp, u64, u64, vp, i32]
+    L.sa_lf.restype = i32
+    L.sa_ibwt.argtypes = [vp, u64, u64, vp, vp, i32]
+    L.sa_ibwt.restype = i32
+    L.sa_ibwt_ex.argtypes = [vp, u64, u64, vp, vp, i32, ctypes.POINTER(u64)]
+    L.sa_ibwt_ex.restype = i32
     DI =ctypes.POINTER(SaDistInfo)
     L.sa_dist_begin.argtypes = [vp, vp, u64, i32, i32, ctypes.POINTER(ctypes.c_uint32), vp, vp, DI]
     L.sa_dist_cuts.argtypes = [vp, ctypes.POINTER(u64), DI]

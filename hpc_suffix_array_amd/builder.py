@@ -651,6 +651,56 @@ def inverse_suffix_array(sa, width: int = 4):
     return out[:n]
 
 
+def _bwt_and_primary(bwt, primary):
+    b = _as_bytes_array(bwt)
+    n = int(b.size)
+    p = int(primary)
+    if p < 0:
+        raise ValueError(f"primary index {p} is negative")
+    return b, n, p   # p >= n is the library's to reject, before any device work
+
+
+def _ibwt_info(words) -> dict:
+    return {"splitters": int(words[0]), "longest_sublist": int(words[1]), "steps": int(words[2])}
+
+
+def lf_mapping(bwt, primary: int, width: int = 4):
+    """LF-mapping of ``(bwt, primary)`` on the GPU (sa_lf), in the convention
+    of :func:`bwt`: order the rows ``primary, 0, 1, ..`` (the primary row
+    first, the rest in rank order) and sort them stably by their byte;
+    ``lf[r]`` is where row r lands.  For the BWT of a text it is the rank of
+    the suffix one position to the left: ``lf[isa[i]] == isa[i - 1]`` and
+    ``lf[primary] == isa[n - 1]``.  uint32 (width 4) or int64 (width 8); a
+    permutation of 0 .. n-1 whatever the bytes are."""
+    if width not in (4, 8):
+        raise ValueError("width must be 4 or 8")
+    b, n, p = _bwt_and_primary(bwt, primary)
+    out = np.empty(max(n, 1), dtype=np.uint32 if width == 4 else np.int64)
+    N.check(N.lib().sa_lf(b.ctypes.data if n else None, n, p, out.ctypes.data, width), "sa_lf")
+    return out[:n]
+
+
+def inverse_bwt(bwt, primary: int, return_sa: bool = False, width: int = 4, return_info: bool = False):
+    """The text whose Burrows-Wheeler transform is ``(bwt, primary)``, on the
+    GPU (sa_ibwt): the inverse of :func:`bwt`.  Returns the text as a uint8
+    array; with ``return_sa`` ``(text, sa)``, the suffix array (uint32 or
+    int64 by ``width``) coming out of the same walk; with ``return_info`` a
+    dict is appended: ``splitters`` and ``longest_sublist`` of the list
+    ranking and ``steps``, n - 1 for a BWT.
+
+    A pair that is the BWT of no text raises SAError, "not a BWT"."""
+    if width not in (4, 8):
+        raise ValueError("width must be 4 or 8")
+    b, n, p = _bwt_and_primary(bwt, primary)
+    text = np.empty(max(n, 1), dtype=np.uint8)
+    sa = np.empty(max(n, 1), dtype=np.uint32 if width == 4 else np.int64) if return_sa else None
+    info = (ctypes.c_uint64 * N.IBWT_INFO)()
+    N.check(N.lib().sa_ibwt_ex(b.ctypes.data if n else None, n, p, text.ctypes.data,
+                               sa.ctypes.data if return_sa else None, width, info), "sa_ibwt")
+    out = (text[:n],) + ((sa[:n],) if return_sa else ()) + ((_ibwt_info(info),) if return_info else ())
+    return out[0] if len(out) == 1 else out
+
+
 class SuffixArray:
     """The reference's SuffixArray object (suffix_array.h:16-21) driven
     through the drop-in C symbols of libsa_hip.so.
@@ -911,6 +961,25 @@ class DeviceBuilder:
         Waits for ``stream``; raises SAError when d_sa is not a permutation."""
         s = _stream(stream)
         N.check(self.L.sa_inverse_device(self.ctx, n, self._ptr(d_sa), self._ptr(d_isa), s), "sa_inverse_device")
+
+    def lf(self, d_bwt, n: int, primary: int, d_lf, stream=None) -> None:
+        """LF-mapping of the n BWT bytes at d_bwt (any byte alignment) with
+        primary index ``primary`` into the n uint32 at d_lf (sa_lf_device;
+        see lf_mapping).  Enqueued on ``stream``; does not wait for it."""
+        s = _stream(stream)
+        N.check(self.L.sa_lf_device(self.ctx, self._ptr(d_bwt), n, primary, self._ptr(d_lf), s), "sa_lf_device")
+
+    def ibwt(self, d_bwt, n: int, primary: int, d_text, d_sa=None, stream=None) -> dict:
+        """Inverse BWT in HBM (sa_ibwt_device): the text of (d_bwt, primary)
+        into the n bytes at d_text (any byte alignment, not d_bwt) and, when
+        ``d_sa`` is given, its suffix array into the n uint32 there.  One host
+        wait.  Returns the info dict of inverse_bwt.  A pair that is no BWT
+        raises SAError, "not a BWT", and leaves d_text and d_sa untouched."""
+        s = _stream(stream)
+        info = (ctypes.c_uint64 * N.IBWT_INFO)()
+        N.check(self.L.sa_ibwt_device(self.ctx, self._ptr(d_bwt), n, primary, self._ptr(d_text), self._opt(d_sa),
+                                      info, s), "sa_ibwt_device")
+        return _ibwt_info(info)
 
     def locate(self, n: int, d_sa, d_lo, d_hi, nq: int, d_off, d_pos, pos_cap: int, max_hits: int = 0,
                order: str = "text", stream=None, _chunks: bool = False) -> int:

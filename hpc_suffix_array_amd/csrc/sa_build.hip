@@ -2482,6 +2482,11 @@ static int scan_i64(int64_t* d_v, uint64_t m, hipStream_t s) {
 // with the comparison as a parameter
 #include "sa_repeats.h"
 
+// the LF-mapping of a BWT and the inverse transform (text and SA back from
+// bwt and primary index): a counting sort by byte, then list ranking over
+// hashed splitters
+#include "sa_ibwt.h"
+
 extern "C" {
 
 int sa_running_max_i64_device(int64_t* d_v, uint64_t m, void* stream) {

@@ -354,6 +354,59 @@ int sa_inverse_device(sa_context* ctx, uint64_t n, const uint32_t* d_sa, uint32_
  * entries outside [0, n) are SA_E_INVALID before any device work). */
 int sa_inverse(const void* sa, uint64_t n, int sa_width, void* isa_out /* width sa_width */);
 
+/* ---- LF-mapping and inverse Burrows-Wheeler transform ---------------------
+ * (csrc/sa_ibwt.h).  The BWT convention above: n bytes, no sentinel, and the
+ * primary index p < n, the rank with bwt[p] = text[n - 1].
+ *   LF        order the rows p, 0, 1, .., p - 1, p + 1, .., n - 1 and sort them
+ *             stably by their byte bwt[r]: LF[r] is where row r lands.  With
+ *             C[c] = the bytes below c and last = bwt[p]: LF[p] = C[last], and
+ *             for r != p, LF[r] = C[c] + [c == last] + #{k < r, k != p,
+ *             bwt[k] == c}, c = bwt[r].  For a genuine BWT, LF[ISA[i]] =
+ *             ISA[i - 1] (i >= 1) and LF[p] = ISA[n - 1]: the rank of the
+ *             suffix one position to the left.  For any bytes and any p < n it
+ *             is a permutation of [0, n).
+ *   inverse   r_0 = LF[p], text[n - 1] = bwt[p]; for k = 1 .. n - 1:
+ *             text[n - 1 - k] = bwt[r_{k-1}], r_k = LF[r_{k-1}], SA[r_k] =
+ *             n - 1 - k.  (bwt, p) is the BWT of a text, which is then unique,
+ *             exactly when this chain meets p for the first time at step
+ *             n - 1 (LF is one cycle of n ranks).  Anything else is
+ *             SA_E_INVALID, "not a BWT" in sa_last_error(), with the outputs
+ *             untouched: never a hang, never a load outside the buffers.
+ * Info words of the inverse, SA_IBWT_INFO uint64: [0] the splitters of the list
+ * ranking (about n / 64 + 1), [1] the longest stretch of the chain between two
+ * splitters (the longest dependent walk of a lane), [2] the steps from r_0
+ * until p: n - 1 for a BWT, fewer when the chain closed early. */
+#define SA_IBWT_INFO 3
+
+/* d_bwt: n bytes at any alignment, d_lf: n uint32, in device memory; n <= 2^32
+ * - 1.  Asynchronous on `stream`: no host wait (ctx names the device).
+ * Temporaries are stream-ordered, n / 32 bytes.  Checked before any HIP call,
+ * each SA_E_INVALID: a NULL ctx; n too large; with n > 0 a NULL d_bwt or d_lf,
+ * primary >= n, d_lf == d_bwt, a d_lf that is not 4-byte aligned.  n == 0 is
+ * SA_OK without a launch.  Exactly d_lf[0, n) is written. */
+int sa_lf_device(sa_context* ctx, const uint8_t* d_bwt, uint64_t n, uint64_t primary, uint32_t* d_lf, void* stream);
+/* d_text: n bytes at any alignment, exactly d_text[0, n) is written; d_sa: n
+ * uint32 or NULL (the suffix array comes out of the same walk).  Host waits
+ * per call: one (the info words, after everything is enqueued; `stream` is
+ * synchronised on return).  Temporaries are stream-ordered, about 4.5 n bytes
+ * (LF itself is 4 n of them).  Checked before any HIP call, each
+ * SA_E_INVALID: a NULL ctx; n too large; with n > 0 a NULL d_bwt or d_text,
+ * primary >= n, d_text == d_bwt, d_sa == d_bwt or d_text, a d_sa that is not
+ * 4-byte aligned.  n == 0 is SA_OK without a device, info zeroed.  On "not a
+ * BWT" info is filled and neither d_text nor d_sa is written. */
+int sa_ibwt_device(sa_context* ctx, const uint8_t* d_bwt, uint64_t n, uint64_t primary, uint8_t* d_text,
+                   uint32_t* d_sa /* or NULL */, uint64_t* info /* host, SA_IBWT_INFO words, or NULL */, void* stream);
+/* Host in, host out: lf_out and sa_out have `width` bytes per entry (4 or 8).
+ * Checked before any device work: the width, n, NULL pointers with n > 0,
+ * primary >= n, outputs that alias an input.  n == 0 is SA_OK without a
+ * device.  They allocate, use and free device buffers.  sa_ibwt_ex is sa_ibwt
+ * with the info words (zeroed first). */
+int sa_lf(const uint8_t* bwt, uint64_t n, uint64_t primary, void* lf_out, int width);
+int sa_ibwt(const uint8_t* bwt, uint64_t n, uint64_t primary, uint8_t* text_out, void* sa_out /* or NULL */,
+            int sa_width);
+int sa_ibwt_ex(const uint8_t* bwt, uint64_t n, uint64_t primary, uint8_t* text_out, void* sa_out /* or NULL */,
+               int sa_width, uint64_t* info /* SA_IBWT_INFO words, or NULL */);
+
 /* ---- batched locate: sorted hit lists in CSR form ------------------------
  * (csrc/sa_locate.h).  Inputs are a suffix array of n entries and nq SA
  * intervals [lo[q], hi[q]) -- what sa_find or sa_match return.  With
