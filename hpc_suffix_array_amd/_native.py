@@ -80,6 +80,15 @@ IBWT_INFO = 3
 LF_TILE = 32768
 IBWT_S = 64
 IBWT_TILE = 16384
+# sa_fm (include/sa_hip.h SA_FM_INFO, SA_FM_MAX_SAMPLE): the info words of the
+# build ([0] sigma, [1] the class, [2] the bytes of the index, [3] the samples);
+# FM_ROWS: the BWT bytes per rank block of the three classes (up to 4, up to 16,
+# more distinct bytes; csrc/sa_fm.h fm_rows); FM_MAX_SAMPLE: the largest
+# sa_sample; FM_HEADER: the bytes of the index's header
+FM_INFO = 4
+FM_ROWS = (64, 256, 4096)
+FM_MAX_SAMPLE = 4096
+FM_HEADER = 4096
 
 # every symbol include/*.h declares
 DROPIN_SYMBOLS = ["create_suffix_array", "destroy_suffix_array", "build_suffix_array",
@@ -97,6 +106,8 @@ EXT_SYMBOLS = ["sa_context_create", "sa_context_destroy", "sa_context_set_debug"
                "sa_lpf_device", "sa_lpf", "sa_lz77_device", "sa_lz77",
                "sa_repeats_device", "sa_repeats",
                "sa_lf_device", "sa_ibwt_device", "sa_lf", "sa_ibwt", "sa_ibwt_ex",
+               "sa_fm_index_bytes", "sa_fm_build_device", "sa_fm_count_device", "sa_fm_locate_device",
+               "sa_fm_build", "sa_fm_count", "sa_fm_locate",
                "sa_dist_begin", "sa_dist_cuts", "sa_dist_plan_cuts", "sa_dist_reserve", "sa_dist_release", "sa_dist_round1", "sa_dist_req_count", "sa_dist_req_fill",
                "sa_dist_answer", "sa_dist_refine",
                "sa_last_error", "sa_host_syncs", "sa_device_count", "sa_version", "sa_struct_size"]
@@ -341,6 +352,21 @@ def lib() -> ctypes.CDLL:
     L.sa_ibwt.restype = i32
     L.sa_ibwt_ex.argtypes = [vp, u64, u64, vp, vp, i32, ctypes.POINTER(u64)]
     L.sa_ibwt_ex.restype = i32
+    u32 = ctypes.c_uint32
+    L.sa_fm_index_bytes.argtypes = [u64, u32]
+    L.sa_fm_index_bytes.restype = u64
+    L.sa_fm_build_device.argtypes = [vp, vp, u64, u64, vp, u32, vp, u64, ctypes.POINTER(u64), vp]
+    L.sa_fm_build_device.restype = i32
+    L.sa_fm_count_device.argtypes = [vp, u64, vp, u64, vp, u64, vp, vp, vp]
+    L.sa_fm_count_device.restype = i32
+    L.sa_fm_locate_device.argtypes = [vp, vp, u64, vp, vp, u64, u64, u32, vp, vp, u64, ctypes.POINTER(u64), vp]
+    L.sa_fm_locate_device.restype = i32
+    L.sa_fm_build.argtypes = [vp, u64, u64, vp, i32, u32, vp, u64, ctypes.POINTER(u64)]
+    L.sa_fm_build.restype = i32
+    L.sa_fm_count.argtypes = [vp, u64, vp, vp, u64, vp, vp]
+    L.sa_fm_count.restype = i32
+    L.sa_fm_locate.argtypes = [vp, u64, vp, vp, u64, u64, u32, vp, vp, i32, u64]
+    L.sa_fm_locate.restype = i32
     DI =ctypes.POINTER(SaDistInfo)
     L.sa_dist_begin.argtypes = [vp, vp, u64, i32, i32, ctypes.POINTER(ctypes.c_uint32), vp, vp, DI]
     L.sa_dist_cuts.argtypes = [vp, ctypes.POINTER(u64), DI]

@@ -842,6 +842,132 @@ class SuffixArray:
         self.close()
 
 
+class FMIndex:
+    """An FM-index of a text, built on the GPU (sa_fm_build): counts and
+    locates patterns with neither the text nor the suffix array, in about
+    1.25 n bytes plus 8 n / sa_sample for the samples (1.5625 n at the default
+    32; ``sa_sample=0``: count only).  The index is one flat byte buffer
+    (``to_bytes`` / ``from_bytes``) held in host memory; every query stages it
+    to the GPU as the other host forms stage the text and the SA
+    (``DeviceBuilder.fm_*`` keeps it in HBM).
+
+    >>> fm = FMIndex.from_text(b"banana"); fm.count([b"ana"])   -> [2]
+    >>> fm.locate([b"ana"])                                      -> ([0, 2], [1, 3])
+    """
+
+    def __init__(self, buf: np.ndarray):
+        buf = np.ascontiguousarray(buf, dtype=np.uint8).reshape(-1)
+        if buf.size < N.FM_HEADER or bytes(buf[:8]) != b"SAMFIDX1":
+            raise N.SAError("not an FM-index: no header")
+        w = buf[:64].view(np.uint64)                  # FmHeader of csrc/sa_fm.h: n at 16, last .. rec at 32, bytes at 56
+        u = buf[:56].view(np.uint32)
+        self.n = int(w[2])
+        self.sigma = int(u[9])
+        self.sa_sample = int(u[10])
+        if int(w[7]) > buf.size:
+            raise N.SAError(f"not an FM-index: the header states {int(w[7])} bytes, the buffer holds {buf.size}")
+        self._buf = buf[:int(w[7])]
+
+    @property
+    def nbytes(self) -> int:
+        return int(self._buf.size)
+
+    @classmethod
+    def from_bwt(cls, bwt, primary: int, sa=None, sa_sample: int = 32) -> "FMIndex":
+        """From ``(bwt, primary)`` as :func:`bwt` returns them.  ``sa``: the
+        suffix array, sampled every ``sa_sample`` text positions; without it
+        (and ``sa_sample > 0``) it is rebuilt by ``inverse_bwt``."""
+        b, n, p = _bwt_and_primary(bwt, primary)
+        sa_sample = int(sa_sample)
+        if sa_sample < 0:
+            raise ValueError("sa_sample is negative")
+        if sa_sample and n and sa is None:
+            sa = inverse_bwt(b, p, return_sa=True)[1]
+        s = None
+        if sa_sample and n:
+            s = _sa_array(sa)
+            if s.size != n:
+                raise ValueError(f"SA has {s.size} entries for a BWT of {n} bytes")
+        L = N.lib()
+        cap = int(L.sa_fm_index_bytes(n, min(sa_sample, 0xFFFFFFFF)))
+        buf = np.zeros(cap, dtype=np.uint8)
+        info = (ctypes.c_uint64 * N.FM_INFO)()
+        N.check(L.sa_fm_build(b.ctypes.data if n else None, n, p, None if s is None else s.ctypes.data,
+                              8 if s is not None and s.dtype == np.int64 else 4, min(sa_sample, 0xFFFFFFFF),
+                              buf.ctypes.data, cap, info), "sa_fm_build")
+        return cls(buf[:int(info[2])].copy())
+
+    @classmethod
+    def from_sa(cls, text, sa, sa_sample: int = 32) -> "FMIndex":
+        """From a text and its suffix array (the BWT is taken on the GPU)."""
+        t, s = _text_and_sa(text, sa)
+        if t.size == 0:
+            return cls.from_bwt(b"", 0, None, sa_sample)
+        b, p = bwt(t, s)
+        return cls.from_bwt(b, p, s, sa_sample)
+
+    @classmethod
+    def from_text(cls, text, sa_sample: int = 32) -> "FMIndex":
+        """Suffix array, BWT and index in one go, all on the GPU."""
+        t = _as_bytes_array(text)
+        if t.size == 0:
+            return cls.from_bwt(b"", 0, None, sa_sample)
+        return cls.from_sa(t, build_suffix_array(t), sa_sample)
+
+    def to_bytes(self) -> bytes:
+        return self._buf.tobytes()
+
+    @classmethod
+    def from_bytes(cls, data) -> "FMIndex":
+        return cls(np.frombuffer(bytes(data), dtype=np.uint8))
+
+    def find(self, patterns):
+        """``(lo, hi)``, int64: where pattern q occurs, exactly the interval
+        of find_patterns; where it does not, ``(0, 0)`` (not the insertion
+        point).  The empty pattern gives ``(0, n)``."""
+        buf, off = _pack_patterns(patterns)
+        nq = int(off.size) - 1
+        lo = np.zeros(nq, dtype=np.uint64)
+        hi = np.zeros(nq, dtype=np.uint64)
+        N.check(N.lib().sa_fm_count(self._buf.ctypes.data, self.nbytes, buf.ctypes.data if buf.size else None,
+                                    off.ctypes.data, nq, lo.ctypes.data, hi.ctypes.data), "sa_fm_count")
+        return lo.astype(np.int64), hi.astype(np.int64)
+
+    def count(self, patterns) -> np.ndarray:
+        """Occurrences of each pattern (int64)."""
+        lo, hi = self.find(patterns)
+        return hi - lo
+
+    def locate(self, patterns, max_hits: int = 0, order: str = "text"):
+        """``(offsets, positions)`` as locate_batch returns them: the
+        occurrences of pattern q are ``positions[offsets[q]:offsets[q + 1]]``,
+        ascending (``order="sa"``: SA order; at most ``max_hits`` of them, the
+        first in SA order)."""
+        lo, hi = self.find(patterns)
+        return self.locate_intervals(lo, hi, max_hits, order)
+
+    def locate_intervals(self, lo, hi, max_hits: int = 0, order: str = "text", _chunks: bool = False):
+        """locate_intervals with the index in place of the suffix array."""
+        flags = _locate_flags(order, _chunks)
+        if max_hits < 0:
+            raise ValueError("max_hits is negative")
+        lo = np.ascontiguousarray(lo, dtype=np.uint64).reshape(-1)
+        hi = np.ascontiguousarray(hi, dtype=np.uint64).reshape(-1)
+        if lo.size != hi.size:
+            raise ValueError(f"{lo.size} lower and {hi.size} upper bounds")
+        nq = int(lo.size)
+        cnt = np.where(hi >= lo, hi - lo, 0)
+        if max_hits:
+            cnt = np.minimum(cnt, np.uint64(max_hits))
+        total = int(cnt.sum(dtype=np.uint64))
+        off = np.zeros(nq + 1, dtype=np.uint64)
+        pos = np.empty(max(total, 1), dtype=np.uint32)
+        N.check(N.lib().sa_fm_locate(self._buf.ctypes.data, self.nbytes, lo.ctypes.data if nq else None,
+                                     hi.ctypes.data if nq else None, nq, int(max_hits), flags, off.ctypes.data,
+                                     pos.ctypes.data, 4, total), "sa_fm_locate")
+        return off.astype(np.int64), pos[:total].astype(np.int64)
+
+
 class DeviceBuilder:
     """Device-resident builder: text and SA live in HBM (torch tensors or raw
     device pointers).  Holds one sa_context (workspace sized for max_n)."""
@@ -980,6 +1106,47 @@ class DeviceBuilder:
         N.check(self.L.sa_ibwt_device(self.ctx, self._ptr(d_bwt), n, primary, self._ptr(d_text), self._opt(d_sa),
                                       info, s), "sa_ibwt_device")
         return _ibwt_info(info)
+
+    def fm_index_bytes(self, n: int, sa_sample: int = 32) -> int:
+        """Bytes to allocate for the index of n BWT bytes before its alphabet
+        is known (sa_fm_index_bytes)."""
+        return int(self.L.sa_fm_index_bytes(n, sa_sample))
+
+    def fm_build(self, d_bwt, n: int, primary: int, d_index, index_bytes: int, d_sa=None, sa_sample: int = 32,
+                 stream=None) -> dict:
+        """FM-index of the n BWT bytes at d_bwt into the index_bytes >=
+        fm_index_bytes(n, sa_sample) bytes at d_index (16-byte aligned), in
+        HBM (sa_fm_build_device).  ``d_sa``: the suffix array, None iff
+        ``sa_sample`` is 0; it and the text may be freed afterwards.  One
+        host wait.  Returns ``{"sigma", "class", "bytes", "samples"}``."""
+        info = (ctypes.c_uint64 * N.FM_INFO)()
+        N.check(self.L.sa_fm_build_device(self.ctx, self._ptr(d_bwt), n, primary, self._opt(d_sa), int(sa_sample),
+                                          self._ptr(d_index), int(index_bytes), info, _stream(stream)),
+                "sa_fm_build_device")
+        return {"sigma": int(info[0]), "class": int(info[1]), "bytes": int(info[2]), "samples": int(info[3])}
+
+    def fm_count(self, d_index, index_bytes: int, d_pat, pat_bytes: int, d_off, nq: int, d_lo, d_hi,
+                 stream=None) -> None:
+        """Backward search of nq patterns (given as for find) in the index at
+        d_index (sa_fm_count_device): [d_lo[q], d_hi[q]) is find's interval
+        where the pattern occurs and (0, 0) where it does not.  Enqueued on
+        ``stream``; does not wait for it."""
+        N.check(self.L.sa_fm_count_device(self._ptr(d_index), int(index_bytes), self._ptr(d_pat), pat_bytes,
+                                          self._ptr(d_off), nq, self._ptr(d_lo), self._ptr(d_hi), _stream(stream)),
+                "sa_fm_count_device")
+
+    def fm_locate(self, d_index, index_bytes: int, d_lo, d_hi, nq: int, d_off, d_pos, pos_cap: int,
+                  max_hits: int = 0, order: str = "text", stream=None, _chunks: bool = False) -> int:
+        """locate with the index at d_index in place of (n, d_sa)
+        (sa_fm_locate_device): the same outputs, the same sizing call with
+        ``d_pos=None``.  Returns the total number of hits.  Waits for
+        ``stream``."""
+        total = ctypes.c_uint64()
+        N.check(self.L.sa_fm_locate_device(self.ctx, self._ptr(d_index), int(index_bytes), self._ptr(d_lo),
+                                           self._ptr(d_hi), nq, int(max_hits), _locate_flags(order, _chunks),
+                                           self._ptr(d_off), None if d_pos is None else self._ptr(d_pos), int(pos_cap),
+                                           ctypes.byref(total), _stream(stream)), "sa_fm_locate_device")
+        return int(total.value)
 
     def locate(self, n: int, d_sa, d_lo, d_hi, nq: int, d_off, d_pos, pos_cap: int, max_hits: int = 0,
                order: str = "text", stream=None, _chunks: bool = False) -> int:

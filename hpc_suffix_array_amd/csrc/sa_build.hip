@@ -2487,6 +2487,11 @@ static int scan_i64(int64_t* d_v, uint64_t m, hipStream_t s) {
 // hashed splitters
 #include "sa_ibwt.h"
 
+// an FM-index over (bwt, primary): rank blocks counted from the LF kernels'
+// histogram, backward-search counting, locating through a sampled SA whose
+// hit lists sa_locate.h sorts
+#include "sa_fm.h"
+
 extern "C" {
 
 int sa_running_max_i64_device(int64_t* d_v, uint64_t m, void* stream) {

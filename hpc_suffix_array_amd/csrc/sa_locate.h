@@ -469,9 +469,11 @@ static int locate_check_args(const sa_context* c, uint64_t n, const uint32_t* d_
 // Host waits: one when no query is large (or nothing is written); with large
 // queries one more per sorted chunk (the radix sort's own), one when the
 // chunks have to be cut on the host, and one at the end.
-static int locate_device(sa_context* c, uint64_t n, const uint32_t* d_sa, const uint32_t* d_lo, const uint32_t* d_hi,
-                         uint64_t nq, uint64_t max_hits, uint32_t flags, uint64_t* d_off, uint32_t* d_pos,
-                         uint64_t pos_cap, uint64_t* total, hipStream_t s) {
+// pos_n: the entries of d_sa are below pos_n (n for a suffix array; sa_fm.h
+// sorts hit lists whose entries are text positions of a longer text)
+static int locate_device_n(sa_context* c, uint64_t n, const uint32_t* d_sa, const uint32_t* d_lo, const uint32_t* d_hi,
+                           uint64_t nq, uint64_t max_hits, uint32_t flags, uint64_t* d_off, uint32_t* d_pos,
+                           uint64_t pos_cap, uint64_t* total, hipStream_t s, uint64_t pos_n) {
     SA_TRY(locate_check_args(c, n, d_sa, d_lo, d_hi, nq, flags, d_off, d_pos, total));
     *total = 0;
     SA_HIP(hipSetDevice(c->device));
@@ -551,7 +553,7 @@ static int locate_device(sa_context* c, uint64_t n, const uint32_t* d_sa, const 
                 cuts.emplace_back(j, (uint64_t)h_ls[j]);
     }
     cuts.emplace_back(n_large, large_hits);
-    const uint32_t pos_bits = locate_bits(n);
+    const uint32_t pos_bits = locate_bits(pos_n);
     for (size_t k = 0; k + 1 < cuts.size(); ++k) {
         const uint64_t j0 = cuts[k].first, j1 = cuts[k + 1].first;
         const uint64_t e0 = cuts[k].second, m = cuts[k + 1].second - e0;
@@ -575,6 +577,12 @@ static int locate_device(sa_context* c, uint64_t n, const uint32_t* d_sa, const 
     }
     SA_HIP(host_sync(s));
     return SA_OK;
+}
+
+static int locate_device(sa_context* c, uint64_t n, const uint32_t* d_sa, const uint32_t* d_lo, const uint32_t* d_hi,
+                         uint64_t nq, uint64_t max_hits, uint32_t flags, uint64_t* d_off, uint32_t* d_pos,
+                         uint64_t pos_cap, uint64_t* total, hipStream_t s) {
+    return locate_device_n(c, n, d_sa, d_lo, d_hi, nq, max_hits, flags, d_off, d_pos, pos_cap, total, s, n);
 }
 
 // host in, host out (sa_locate), over the steps of sa_host.h: the offsets and

@@ -407,6 +407,105 @@ int sa_ibwt(const uint8_t* bwt, uint64_t n, uint64_t primary, uint8_t* text_out,
 int sa_ibwt_ex(const uint8_t* bwt, uint64_t n, uint64_t primary, uint8_t* text_out, void* sa_out /* or NULL */,
                int sa_width, uint64_t* info /* SA_IBWT_INFO words, or NULL */);
 
+/* ---- FM-index: backward-search count and sampled locate --------------------
+ * (csrc/sa_fm.h).  An index over (bwt, primary) in the convention above that
+ * answers count and locate with neither the text nor the suffix array in
+ * memory: about 1.25 n bytes without samples, 1.5625 n with sa_sample = 32.
+ * With last = bwt[p], C[c] = the bytes below c in the BWT, base[c] = C[c] +
+ * [c == last], occ(c, r) = #{k < r : bwt[k] == c} and occ'(c, r) = occ(c, r) -
+ * [c == last and r > p]:
+ *   count     P[0, m): lo = C[c], hi = C[c + 1] for c = P[m - 1], then for c =
+ *             P[m - 2] .. P[0] while lo < hi: lo = base[c] + occ'(c, lo), hi =
+ *             base[c] + occ'(c, hi).  When the pattern occurs, [lo, hi) is
+ *             exactly sa_find's interval.  When it does not, the answer is
+ *             lo == hi == 0: NOT sa_find's insertion point.  The empty pattern
+ *             gives [0, n).
+ *   locate    row r is marked iff SA[r] % sa_sample == 0 and sample[rank1(r)] =
+ *             SA[r] / sa_sample; SA[r] = sa_sample * sample[rank1(q)] + k for
+ *             the first marked q = LF^k[r], k < sa_sample, LF[r] = base[bwt[r]] +
+ *             occ'(bwt[r], r).
+ * The index is one position-independent byte buffer (offsets, never pointers)
+ * that may be copied, written to disk and read back at any 16-byte aligned
+ * address: a 4096-byte header, rank blocks of [cols x uint32 counts][R BWT
+ * bytes] with (cols, R) = (4, 64) for up to 4 distinct bytes, (16, 256) for up
+ * to 16, (256, 4096) otherwise, and with samples one mark bit per row (64-bit
+ * words, per-word and per-tile counts) and ceil(n / sa_sample) uint32 samples.
+ * Info words of the build, SA_FM_INFO uint64: [0] sigma, the distinct bytes,
+ * [1] the class 0 / 1 / 2, [2] the bytes of the index (<= sa_fm_index_bytes),
+ * [3] the samples. */
+#define SA_FM_INFO 4
+#define SA_FM_MAX_SAMPLE 4096
+
+/* Pure host arithmetic: the largest of the three classes' sizes, so that the
+ * caller allocates before sigma is known.  sa_sample == 0: no locate.  For
+ * sa_sample = 32 and n >= 2^20 it is at most 1.6 n + 64 KiB. */
+uint64_t sa_fm_index_bytes(uint64_t n, uint32_t sa_sample);
+
+/* d_bwt: n bytes at any alignment; d_sa: the n uint32 of the suffix array, NULL
+ * iff sa_sample == 0; d_index: index_bytes bytes, 16-byte aligned; all in device
+ * memory; n <= 2^32 - 1, sa_sample 0 or 1 .. SA_FM_MAX_SAMPLE.  Host waits
+ * per call: one (the byte counts: sigma decides the class); what follows is
+ * enqueued on `stream` and not waited for.  Temporaries are stream-ordered,
+ * n / 32 bytes.  Checked before any HIP call, each SA_E_INVALID with its own
+ * message: a NULL ctx; n too large; sa_sample above SA_FM_MAX_SAMPLE; a NULL or
+ * misaligned d_index; index_bytes below sa_fm_index_bytes(n, sa_sample); with
+ * n > 0 a NULL d_bwt, primary >= n, sa_sample > 0 with a NULL d_sa or the
+ * reverse, a d_sa that is not 4-byte aligned, d_index == d_bwt or d_sa.
+ * n == 0 is SA_OK with a valid empty index.  d_sa is trusted to be the suffix
+ * array: one that is not gives an index whose locate answers are wrong, never a
+ * store outside d_index. */
+int sa_fm_build_device(sa_context* ctx, const uint8_t* d_bwt, uint64_t n, uint64_t primary,
+                       const uint32_t* d_sa /* NULL iff sa_sample == 0 */, uint32_t sa_sample, void* d_index,
+                       uint64_t index_bytes, uint64_t* info /* host, SA_FM_INFO words, or NULL */, void* stream);
+/* Patterns and results as sa_find_device's: pattern q is bytes d_pat_off[q] ..
+ * d_pat_off[q + 1] of d_pat, the offsets clamped to pat_bytes and a decreasing
+ * pair the empty pattern; [d_lo[q], d_hi[q]) uint32.  Asynchronous on `stream`:
+ * no host wait, no context, no workspace; SA_OK without a launch when nq == 0.
+ * The kernel reads the header itself: when the magic, the version, n or a
+ * section's extent does not fit index_bytes every query answers (0, 0); every
+ * computed row is clamped to n, so no load leaves d_index[0, index_bytes)
+ * whatever the bytes are, and every search ends after m steps.  Checked before
+ * any HIP call (SA_E_INVALID): a NULL pointer, a d_index that is not 16-byte
+ * aligned, nq too large. */
+int sa_fm_count_device(const void* d_index, uint64_t index_bytes, const uint8_t* d_pat, uint64_t pat_bytes,
+                       const uint64_t* d_pat_off, uint64_t nq, uint32_t* d_lo, uint32_t* d_hi, void* stream);
+/* sa_locate_device with the index in place of (n, d_sa): d_off, d_pos,
+ * max_hits, SA_LOCATE_SA_ORDER, the sizing call (d_pos NULL or *total >
+ * pos_cap) and pos_cap mean the same, pos[off[q] .. off[q + 1]) = SA[lo[q] ..
+ * lo[q] + c[q]) sorted ascending.  A group of 1 / 4 / 64 lanes (by class) per
+ * hit resolves SA[row] by the walk above, bounded at sa_sample steps; on a
+ * corrupt index the result is clamped below n.  The hits are materialised (4
+ * bytes each, stream-ordered) and sorted per query by sa_locate_device's
+ * kernels.  Host waits: one for the total and the header's words, then
+ * sa_locate_device's own, or one at the end with SA_LOCATE_SA_ORDER.
+ * SA_E_INVALID: what is no index ("not an FM-index"), an index built with
+ * sa_sample == 0 ("no samples"), a total above 2^32 - 1 ("cap it with
+ * max_hits"); and before any HIP call a NULL ctx, d_index, d_lo, d_hi, d_off
+ * or total, a misaligned d_index, nq too large, unknown flags. */
+int sa_fm_locate_device(sa_context* ctx, const void* d_index, uint64_t index_bytes, const uint32_t* d_lo,
+                        const uint32_t* d_hi, uint64_t nq, uint64_t max_hits, uint32_t flags,
+                        uint64_t* d_off /* nq + 1 */, uint32_t* d_pos /* may be NULL */, uint64_t pos_cap,
+                        uint64_t* total, void* stream);
+/* Host in, host out, over the staging of the other host forms; they allocate,
+ * use and free device buffers.  sa_fm_build: sa has sa_width (4 or 8) bytes per
+ * entry, NULL iff sa_sample == 0; index_out holds index_bytes >=
+ * sa_fm_index_bytes(n, sa_sample) bytes, of which info[2] are written; n == 0
+ * writes the empty index without a device.  sa_fm_count and sa_fm_locate check
+ * the header on the host, SA_E_INVALID "not an FM-index" (index_bytes below
+ * the header, a wrong magic or version, a section that ends past index_bytes);
+ * lo_out / hi_out are uint64; sa_fm_locate fills off_out on the host as
+ * sa_locate does, rejects lo > hi or hi > n, and writes pos_out with pos_width
+ * (4 or 8) bytes per entry.  Over an empty index both return without a
+ * device. */
+int sa_fm_build(const uint8_t* bwt, uint64_t n, uint64_t primary, const void* sa /* NULL iff sa_sample == 0 */,
+                int sa_width, uint32_t sa_sample, void* index_out, uint64_t index_bytes,
+                uint64_t* info /* SA_FM_INFO words, or NULL */);
+int sa_fm_count(const void* index, uint64_t index_bytes, const uint8_t* pat, const uint64_t* pat_off, uint64_t nq,
+                uint64_t* lo_out, uint64_t* hi_out);
+int sa_fm_locate(const void* index, uint64_t index_bytes, const uint64_t* lo, const uint64_t* hi, uint64_t nq,
+                 uint64_t max_hits, uint32_t flags, uint64_t* off_out /* nq + 1 */, void* pos_out, int pos_width,
+                 uint64_t pos_cap);
+
 /* ---- batched locate: sorted hit lists in CSR form ------------------------
  * (csrc/sa_locate.h).  Inputs are a suffix array of n entries and nq SA
  * intervals [lo[q], hi[q]) -- what sa_find or sa_match return.  With
