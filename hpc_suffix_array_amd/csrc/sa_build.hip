@@ -1927,6 +1927,12 @@ static int place_by_permutation(sa_context* c, const Src& src, uint64_t n, uint3
     return SA_OK;
 }
 
+// the stripes place_by_permutation runs with when `stripes` are asked for
+// (SA_TRACE: a context too small for the regions runs one)
+static uint32_t perm_stripes_run(const sa_context* c, uint64_t n, uint32_t stripes) {
+    return plan_stripes(c, n, plan_check(n, kChkSubA), stripes).st;
+}
+
 // sa_check.h: pass A (ISA' by permutation) and pass B (adjacent keys compared
 // in LDS per sorted sub-bin); one host sync at the end.  Workspace: ISA' in
 // rank, pairs in keys[0] / keys[1], cursors in hist, sub-bin end keys in
@@ -1945,6 +1951,7 @@ static int check_device(sa_context* c, const uint8_t* d_text, uint64_t n, const 
     uint64_t* ends = reinterpret_cast<uint64_t*>(c->vals_alt);
     for (uint32_t stripes : {kChkStripes, 1u}) {
         SA_HIP(hipMemsetAsync(err, 0, 4, s));
+        uint32_t ran[2] = {1, 1};   // the stripes plan_stripes granted (SA_TRACE)
         for (int pass = 0; pass < 2; ++pass) {
             // pass B's sub-bins: 2^13, or 2^14 once a bin would split into more
             // than the split pass's kPermMaxSub (n > 2^31)
@@ -1954,6 +1961,7 @@ static int check_device(sa_context* c, const uint8_t* d_text, uint64_t n, const 
             if (p.nb1 > 1024 || p.nsub > kPermMaxSub || p.s1 > 24)
                 return set_err(SA_E_INTERNAL, "checker plan out of range (n=%llu)", (unsigned long long)n);
             const BinStripes bs = plan_stripes(c, n, p, stripes);
+            ran[pass] = bs.st;
             const uint64_t* placed =
                 pass == 0 ? permute_levels<ChkSrcA, 32, 1>(c, ChkSrcA{d_sa}, n, p, bs, err, s, &rc)
                           : permute_levels<ChkSrcB, 40, 1>(c, ChkSrcB{isa, d_text}, n, p, bs, err, s, &rc);
@@ -1980,7 +1988,8 @@ static int check_device(sa_context* c, const uint8_t* d_text, uint64_t n, const 
         SA_HIP(hipGetLastError());
         SA_HIP(hipMemcpyAsync(c->host_words + 3, err, 4, hipMemcpyDeviceToHost, s));
         SA_HIP(host_sync(s));
-        SA_TRACE("check (%u stripes): error bits %#x", stripes, c->host_words[3]);
+        SA_TRACE("check (%u stripes asked, %u / %u run in pass A / B): error bits %#x", stripes, ran[0], ran[1],
+                 c->host_words[3]);
         if (!(c->host_words[3] & 128u)) break;   // else a stripe overflowed: again with one
     }
     return c->host_words[3] == 0 ? 1 : 0;
@@ -2015,10 +2024,15 @@ static int lcp_device(sa_context* c, const uint8_t* d_text, uint64_t n, const ui
     for (uint32_t stripes : {kChkStripes, 1u}) {
         SA_HIP(hipMemsetAsync(c->words + 12, 0, 4, s));
         SA_TRY(place_by_permutation<PhiSrc, 2>(c, PhiSrc{d_sa}, n, phi, c->words + 12, s, stripes));
-        if (stripes == 1) break;
+        if (stripes == 1) {
+            SA_TRACE("lcp PHI (%u stripes asked, %u run)", stripes, perm_stripes_run(c, n, stripes));
+            break;
+        }
         // a level-1 stripe that overflowed (only an adversarial SA) lost pairs
         SA_HIP(hipMemcpyAsync(c->host_words + 12, c->words + 12, 4, hipMemcpyDeviceToHost, s));
         SA_HIP(host_sync(s));
+        SA_TRACE("lcp PHI (%u stripes asked, %u run): error bits %#x", stripes, perm_stripes_run(c, n, stripes),
+                 c->host_words[12]);
         if (!(c->host_words[12] & 128u)) break;
     }
     hipLaunchKernelGGL(k_plcp_irreducible, dim3(grid), dim3(kBlock), 0, s, d_text, n, (const uint32_t*)phi, v,
@@ -2052,9 +2066,15 @@ static int lcp_device(sa_context* c, const uint8_t* d_text, uint64_t n, const ui
                 else
                     SA_TRY(place_by_permutation<PlcpSrc, 4>(c, PlcpSrc{isa1, v}, n, d_lcp, c->words + 12, s,
                                                             stripes));
-                if (stripes == 1) break;
+                if (stripes == 1) {
+                    SA_TRACE("lcp %s (%u stripes asked, %u run)", pass ? "PLCP" : "ISA", stripes,
+                             perm_stripes_run(c, n, stripes));
+                    break;
+                }
                 SA_HIP(hipMemcpyAsync(c->host_words + 12, c->words + 12, 4, hipMemcpyDeviceToHost, s));
                 SA_HIP(host_sync(s));
+                SA_TRACE("lcp %s (%u stripes asked, %u run): error bits %#x", pass ? "PLCP" : "ISA", stripes,
+                         perm_stripes_run(c, n, stripes), c->host_words[12]);
                 if (!(c->host_words[12] & 128u)) break;
             }
         }

@@ -311,7 +311,7 @@ static int inverse_device(sa_context* c, uint64_t n, const uint32_t* d_sa, uint3
         SA_HIP(hipGetLastError());
         SA_HIP(hipMemcpyAsync(c->host_words + 12, err, 4, hipMemcpyDeviceToHost, s));
         SA_HIP(host_sync(s));
-        SA_TRACE("inverse (%u stripes): error bits %#x", stripes, c->host_words[12]);
+        SA_TRACE("inverse (%u stripes asked, %u run): error bits %#x", stripes, bs.st, c->host_words[12]);
         if (!(c->host_words[12] & 128u)) break;   // else a stripe overflowed: again with one
     }
     if (c->host_words[12]) return set_err(SA_E_INVALID, "SA is not a permutation of [0, n) (error bits %#x)", c->host_words[12]);

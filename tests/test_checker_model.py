@@ -8,7 +8,8 @@ no holes), pass B places at r = ISA[i] the key (text[i] << 32 | ISA'[i+1])
 (ISA'[n] = 0) and checks that the keys rise strictly along r.  This file
 checks that the two verdicts agree on valid suffix arrays and on every kind of
 corruption (host only; the kernels themselves are tested on the GPU by
-tests/test_gpu_parity.py::test_checker_permutation_passes)."""
+tests/test_gpu_parity.py::test_checker_permutation_passes and, with eight
+stripes per bin, by tests/test_gpu_perm_stripes.py)."""
 import numpy as np
 import pytest
 
