@@ -1019,8 +1019,11 @@ class DeviceBuilder:
                             "sa_check_device"))
 
     def lcp(self, d_text, n: int, d_sa, d_lcp, stream=None) -> tuple:
-        """LCP of the SA at d_sa into the n uint32 at d_lcp; returns the longest
-        repeated substring as (length, SA position)."""
+        """LCP of the SA at d_sa into the n uint32 at d_lcp (16-byte aligned,
+        not d_sa: the placement stores 16 bytes at a time; a misaligned d_lcp
+        raises SAError before any launch); returns the longest repeated
+        substring as (length, SA position).  d_sa must be a valid suffix array
+        of the text (check).  Waits for ``stream``."""
         s = _stream(stream)
         ln, pos = ctypes.c_uint64(), ctypes.c_uint64()
         N.check(self.L.sa_lcp_device(self.ctx, self._ptr(d_text), n, self._ptr(d_sa), self._ptr(d_lcp),

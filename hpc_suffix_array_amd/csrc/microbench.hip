@@ -121,7 +121,7 @@ int main(int argc, char** argv) {
     uint32_t* totals = ws + 16384 + 524288;
     CK(hipMemset(ghist, 0, 4096 * 4));
     SrcKeys src{k0, v0};
-    hipLaunchKernelGGL(k_global_hist<SrcKeys>, dim3(2048), dim3(kBlock), 0, 0, src, n, 1u, ghist);
+    hipLaunchKernelGGL(k_global_hist<SrcKeys>, dim3(2048), dim3(kBlock), 0, 0, src, n, 1u, ghist, ~0ull);
     hipLaunchKernelGGL(k_digit_base, dim3(1), dim3(kBlock), 0, 0, (const uint32_t*)ghist, base);
     CK(hipDeviceSynchronize());
     Timer T;

@@ -165,6 +165,7 @@ struct sa_context {
     uint32_t* segw = nullptr;                   // second bucket pass: per-segment cursors / bases / flags
     uint64_t* states = nullptr;                 // onesweep tile states [tiles][256]
     uint32_t epoch = 0;                         // onesweep state tag of the last pass
+    uint64_t radix_passes = 0;                  // passes that took a tag since the context was made (SA_TRACE)
     int radix = 0;                              // 0 onesweep, 1 reduce-then-scan
     int cus = 256;                              // compute units (persistent grids)
     uint32_t* member = nullptr;                 // bitmap of round-1 unsorted positions
@@ -478,7 +479,10 @@ static int onesweep_prepare(sa_context* c, hipStream_t s) {
 }
 
 static uint32_t next_epoch(sa_context* c, hipStream_t s) {
+    ++c->radix_passes;
     if (++c->epoch > kEpochMask) {
+        SA_TRACE("epoch wrap: %llu bytes of tile states cleared before radix pass %llu of the context",
+                 (unsigned long long)tile_states_bytes(c->cap), (unsigned long long)c->radix_passes);
         hipMemsetAsync(c->states, 0, tile_states_bytes(c->cap), s);
         c->epoch = 1;
     }
@@ -526,7 +530,8 @@ static int radix_sort(sa_context* c, const Src& first, uint64_t first_bytes, con
             if (rc) return rc;
             tm.begin(k_hist);
             const uint32_t grid = (uint32_t)std::min<uint64_t>((n + kBlock - 1) / kBlock, 2048);
-            hipLaunchKernelGGL(k_global_hist<Src>, dim3(grid), dim3(kBlock), 0, s, first, n, P, os_ghist(c));
+            hipLaunchKernelGGL(k_global_hist<Src>, dim3(grid), dim3(kBlock), 0, s, first, n, P, os_ghist(c),
+                               bits >= 64 ? ~0ull : (1ull << bits) - 1ull);
             tm.end();
             add_bytes(st, k_hist, first_bytes);
         }
@@ -2008,6 +2013,8 @@ static int lcp_device(sa_context* c, const uint8_t* d_text, uint64_t n, const ui
     if (n == 0) return SA_OK;
     if (!d_text || !d_sa || !d_lcp) return set_err(SA_E_INVALID, "NULL device pointer");
     if ((const void*)d_sa == (const void*)d_lcp) return set_err(SA_E_INVALID, "d_lcp may not alias d_sa");
+    // PHI and the final LCP are placed into d_lcp by k_perm_place, which stores uint4
+    if ((uintptr_t)d_lcp & 15) return set_err(SA_E_INVALID, "d_lcp must be 16-byte aligned");
     if (n > 0xFFFFFFFFull) return set_err(SA_E_INVALID, "n too large");
     SA_HIP(hipSetDevice(c->device));
     int rc = ensure_capacity(c, n);

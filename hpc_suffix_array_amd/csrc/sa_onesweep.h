@@ -60,15 +60,18 @@ __device__ __forceinline__ void hist_add_runs(uint32_t (*s_h)[kRadix], uint64_t 
     }
 }
 
-// digit histograms of all `passes` 8-bit digits of the source keys
+// digit histograms of all `passes` 8-bit digits of the source keys.  kmask:
+// the key bits the sort orders by; the scatter passes mask their digit to
+// them, so a key bit above them (sa_sort_pairs_device leaves those to the
+// caller) must not reach the top pass's counts either
 template <class Src>
 __global__ __launch_bounds__(kBlock) void k_global_hist(Src src, uint64_t n, uint32_t passes,
-                                                        uint32_t* __restrict__ ghist) {
+                                                        uint32_t* __restrict__ ghist, uint64_t kmask) {
     __shared__ uint32_t s_h[kMaxPasses][kRadix];
     for (int i = threadIdx.x; i < (int)(kMaxPasses * kRadix); i += kBlock) (&s_h[0][0])[i] = 0;
     __syncthreads();
     for (uint64_t e = (uint64_t)blockIdx.x * kBlock + threadIdx.x; e < n; e += (uint64_t)gridDim.x * kBlock) {
-        hist_add_runs(s_h, src.key(e), passes);
+        hist_add_runs(s_h, src.key(e) & kmask, passes);
     }
     __syncthreads();
     for (uint32_t p = 0; p < passes; ++p) {

@@ -213,7 +213,12 @@ int sa_check(const uint8_t* text, uint64_t n, const void* sa, int sa_width);
  * d_lcp[r] = lcp(SA[r-1], SA[r]) (n uint32 in device memory, may not alias
  * d_sa).  lrs_len / lrs_pos (optional) receive the first r >= 1 with the
  * strictly largest lcp: its length and SA[r] (0, 0 when nothing repeats).
- * Synchronises `stream` before returning. */
+ * d_lcp must be 16-byte aligned: PHI and the final LCP are placed into it by
+ * the coalesced permutation, which stores 16 bytes at a time (nothing past
+ * d_lcp[n - 1] is written); a misaligned d_lcp is SA_E_INVALID, "d_lcp must
+ * be 16-byte aligned", before any launch.
+ * Precondition: d_sa is a valid suffix array of the text (sa_check_device);
+ * it is not checked here.  Synchronises `stream` before returning. */
 int sa_lcp_device(sa_context* ctx, const uint8_t* d_text, uint64_t n, const uint32_t* d_sa, uint32_t* d_lcp,
                   uint64_t* lrs_len, uint64_t* lrs_pos, void* stream);
 /* Host in, host out: sa and lcp_out have width sa_width (4 or 8). */

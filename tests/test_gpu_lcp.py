@@ -122,6 +122,48 @@ def test_lcp_device_builder(gpu, oracle):
     b.close()
 
 
+def test_lcp_device_rejects_a_misaligned_output(gpu, oracle):
+    """PHI and the final LCP are placed into d_lcp by 16-byte stores: a d_lcp
+    that is not 16-byte aligned is refused on the host before any launch (the
+    output keeps its fill), the aligned call right after it is exact, and the
+    host form, which allocates its own buffer, is unaffected."""
+    import torch
+    from hpc_suffix_array_amd import DeviceBuilder, SAError, lcp_array
+    n = 65_537
+    t = oracle.gen_text("dna", n, seed=12)
+    sa = oracle.sa_c(t)
+    ref = oracle.lcp_c(t, sa)
+    d_text = torch.from_numpy(t).cuda()
+    d_sa = torch.from_numpy(sa.view(np.int32)).cuda()
+    d_lcp = torch.full((n + 4,), -1, dtype=torch.int32, device="cuda")
+    assert d_lcp.data_ptr() % 16 == 0
+    torch.cuda.synchronize()
+    b = DeviceBuilder(n)
+    try:
+        waits = gpu.lib().sa_host_syncs()
+        for off in (1, 2, 3):
+            assert d_lcp[off:].data_ptr() % 16 == 4 * off
+            with pytest.raises(SAError, match="aligned"):
+                b.lcp(d_text, n, d_sa, d_lcp[off:off + n])
+        assert gpu.lib().sa_host_syncs() == waits           # refused before any device work: no host wait
+        torch.cuda.synchronize()
+        assert bool((d_lcp == -1).all())
+        ln, pos = b.lcp(d_text, n, d_sa, d_lcp[:n])
+        torch.cuda.synchronize()
+        assert (d_lcp[:n].cpu().numpy().view(np.uint32) == ref).all()
+        assert bool((d_lcp[n:] == -1).all())
+        assert bytes(t[pos:pos + ln]) == oracle.lrs_c(t, sa, ref)
+        ln4, pos4 = b.lcp(d_text, n, d_sa, d_lcp[4:4 + n])   # 16 bytes further on is aligned again
+        torch.cuda.synchronize()
+        assert (ln4, pos4) == (ln, pos) and (d_lcp[4:].cpu().numpy().view(np.uint32) == ref).all()
+    finally:
+        b.close()
+    lcp, _ = lcp_array(t, sa)
+    assert (lcp == ref).all()
+    lcp, _ = lcp_array(t[1:], oracle.sa_c(t[1:]))           # a host text at an odd address
+    assert (lcp == oracle.lcp_c(np.ascontiguousarray(t[1:]), oracle.sa_c(t[1:]))).all()
+
+
 @pytest.mark.slow
 def test_lcp_config3_lrs_known_answer(gpu, oracle, golden):
     """configs[2] (2^30 - 1 DNA): the reference's recorded LRS."""
