@@ -3,8 +3,10 @@ construction behind the C ABI of a-rtemis99/hpc_suffix_array
 (src/common/suffix_array.h) plus a 64-bit extended ABI (include/sa_hip.h).
 """
 from ._native import SAError, build_library, device_count, lib  # noqa: F401
-from .builder import (DeviceBuilder, FMIndex, SuffixArray, build_suffix_array, bwt, check_suffix_array,  # noqa: F401
-                      count_patterns, find_patterns, inverse_bwt, inverse_suffix_array, lcp_array, lf_mapping,
+from .builder import (Collection, DeviceBuilder, FMIndex, SuffixArray, build_suffix_array, bwt,  # noqa: F401
+                      check_suffix_array,
+                      count_patterns, doc_of_positions, document_array, document_frequency, find_patterns, inverse_bwt,
+                      inverse_suffix_array, lcp_array, lf_mapping, list_documents,
                       locate_batch,
                       locate_intervals, locate_patterns, longest_previous_factor, lz77_factorize,
                       match_patterns, matching_statistics, maximal_exact_matches, maximal_repeats)
@@ -12,5 +14,6 @@ from .builder import (DeviceBuilder, FMIndex, SuffixArray, build_suffix_array, b
 __all__ = ["SAError", "DeviceBuilder", "SuffixArray", "build_suffix_array", "check_suffix_array",
            "lcp_array", "find_patterns", "count_patterns", "locate_patterns", "locate_intervals", "locate_batch",
            "match_patterns", "matching_statistics", "maximal_exact_matches", "longest_previous_factor", "lz77_factorize", "maximal_repeats", "bwt", "inverse_suffix_array",
-           "lf_mapping", "inverse_bwt", "FMIndex", "build_library", "device_count",
+           "lf_mapping", "inverse_bwt", "FMIndex", "document_array", "doc_of_positions", "document_frequency",
+           "list_documents", "Collection", "build_library", "device_count",
            "lib"]

@@ -89,6 +89,18 @@ FM_INFO = 4
 FM_ROWS = (64, 256, 4096)
 FM_MAX_SAMPLE = 4096
 FM_HEADER = 4096
+# collections (include/sa_hip.h SA_DOC_*): "no document" of sa_doc_of (-1 in the
+# int64 arrays of the Python interface), the flag that leaves a listing in rank
+# order, and the class boundaries of csrc/sa_docs.h: DOC_TILE ranks per chunk of
+# a long interval (kDocTile), DOC_GROUP_MAX the longest interval one lane group
+# counts (kDocGroupMax), DOC_LDS_DOCS the most documents whose boundaries are
+# searched in LDS (kDocLdsDocs)
+DOC_NONE = 0xFFFFFFFF
+DOC_RANK_ORDER = 1
+DOC_TILE = 2048
+DOC_GROUP_MAX = 256
+DOC_LDS_DOCS = 8192
+DOC_ORDERS = {"doc": 0, "rank": DOC_RANK_ORDER}
 
 # every symbol include/*.h declares
 DROPIN_SYMBOLS = ["create_suffix_array", "destroy_suffix_array", "build_suffix_array",
@@ -108,6 +120,8 @@ EXT_SYMBOLS = ["sa_context_create", "sa_context_destroy", "sa_context_set_debug"
                "sa_lf_device", "sa_ibwt_device", "sa_lf", "sa_ibwt", "sa_ibwt_ex",
                "sa_fm_index_bytes", "sa_fm_build_device", "sa_fm_count_device", "sa_fm_locate_device",
                "sa_fm_build", "sa_fm_count", "sa_fm_locate",
+               "sa_doc_array_device", "sa_doc_of_device", "sa_doc_frequency_device", "sa_doc_list_device",
+               "sa_doc_array", "sa_doc_of", "sa_doc_frequency", "sa_doc_list",
                "sa_dist_begin", "sa_dist_cuts", "sa_dist_plan_cuts", "sa_dist_reserve", "sa_dist_release", "sa_dist_round1", "sa_dist_req_count", "sa_dist_req_fill",
                "sa_dist_answer", "sa_dist_refine",
                "sa_last_error", "sa_host_syncs", "sa_device_count", "sa_version", "sa_struct_size"]
@@ -367,6 +381,22 @@ def lib() -> ctypes.CDLL:
     L.sa_fm_count.restype = i32
     L.sa_fm_locate.argtypes = [vp, u64, vp, vp, u64, u64, u32, vp, vp, i32, u64]
     L.sa_fm_locate.restype = i32
+    L.sa_doc_array_device.argtypes = [vp, u64, vp, vp, u64, vp, vp, vp]
+    L.sa_doc_array_device.restype = i32
+    L.sa_doc_of_device.argtypes = [vp, u64, u64, vp, u64, vp, vp, vp]
+    L.sa_doc_of_device.restype = i32
+    L.sa_doc_frequency_device.argtypes = [u64, vp, vp, vp, u64, vp, vp]
+    L.sa_doc_frequency_device.restype = i32
+    L.sa_doc_list_device.argtypes = [vp, u64, vp, vp, vp, vp, u64, u64, u32, vp, vp, u64, ctypes.POINTER(u64), vp]
+    L.sa_doc_list_device.restype = i32
+    L.sa_doc_array.argtypes = [vp, u64, i32, vp, u64, vp, vp]
+    L.sa_doc_array.restype = i32
+    L.sa_doc_of.argtypes = [vp, u64, u64, vp, u64, i32, vp, vp]
+    L.sa_doc_of.restype = i32
+    L.sa_doc_frequency.argtypes = [vp, u64, i32, vp, vp, u64, vp]
+    L.sa_doc_frequency.restype = i32
+    L.sa_doc_list.argtypes = [vp, vp, u64, i32, vp, vp, u64, u64, u32, vp, vp, u64]
+    L.sa_doc_list.restype = i32
     DI =ctypes.POINTER(SaDistInfo)
     L.sa_dist_begin.argtypes = [vp, vp, u64, i32, i32, ctypes.POINTER(ctypes.c_uint32), vp, vp, DI]
     L.sa_dist_cuts.argtypes = [vp, ctypes.POINTER(u64), DI]

@@ -701,6 +701,129 @@ def inverse_bwt(bwt, primary: int, return_sa: bool = False, width: int = 4, retu
     return out[0] if len(out) == 1 else out
 
 
+def _doc_offsets(doc_off) -> np.ndarray:
+    """The D + 1 offsets of a collection as uint64 (the C side checks their values)."""
+    off = np.asarray(doc_off)
+    if off.ndim != 1 or off.size < 2 or off.dtype.kind not in "iu":
+        raise ValueError("doc_off: a one-dimensional integer array of D + 1 entries, D >= 1")
+    if off.dtype.kind == "i" and (off < 0).any():
+        raise ValueError("doc_off has a negative entry")
+    return np.ascontiguousarray(off, dtype=np.uint64)
+
+
+def _doc_intervals(lo, hi):
+    lo = np.ascontiguousarray(lo, dtype=np.uint64).reshape(-1)
+    hi = np.ascontiguousarray(hi, dtype=np.uint64).reshape(-1)
+    if lo.size != hi.size:
+        raise ValueError(f"{lo.size} lower and {hi.size} upper bounds")
+    return lo, hi
+
+
+def _doc_order(order: str) -> int:
+    if order not in N.DOC_ORDERS:
+        raise ValueError(f"order {order!r}: one of {sorted(N.DOC_ORDERS)}")
+    return N.DOC_ORDERS[order]
+
+
+def document_array(sa, doc_off, prev: bool = True):
+    """The document array of a collection on the GPU (sa_doc_array).
+
+    ``sa`` is the suffix array of the concatenated documents and ``doc_off``
+    their D + 1 non-decreasing offsets (``doc_off[0] == 0``, ``doc_off[D] ==
+    len(sa)``; document d is ``text[doc_off[d]:doc_off[d + 1]]``, empty
+    documents allowed).  Returns ``(da, prv)``, or ``da`` alone with
+    ``prev=False``: ``da[r]`` is the document in which ``sa[r]`` lies and
+    ``prv[r]`` is 1 + the nearest smaller rank of the same document (0: none),
+    what document_frequency and list_documents take.  uint32 for a 32-bit
+    ``sa``, int64 for an int64 one."""
+    s = _sa_array(sa)
+    off = _doc_offsets(doc_off)
+    n, width = int(s.size), 8 if s.dtype == np.int64 else 4
+    dt = np.int64 if width == 8 else np.uint32
+    da = np.empty(max(n, 1), dtype=dt)
+    pv = np.empty(max(n, 1), dtype=dt) if prev else None
+    if n:
+        N.require_device()
+    N.check(N.lib().sa_doc_array(s.ctypes.data if n else None, n, width, off.ctypes.data, int(off.size) - 1,
+                                 da.ctypes.data, pv.ctypes.data if prev else None), "sa_doc_array")
+    return (da[:n], pv[:n]) if prev else da[:n]
+
+
+def doc_of_positions(doc_off, n: int, positions):
+    """(document, offset inside it) of text positions on the GPU (sa_doc_of):
+    two int64 arrays, both -1 for a position that is not below ``n``.
+    ``positions``: what locate_intervals returns."""
+    off = _doc_offsets(doc_off)
+    pos = np.ascontiguousarray(positions, dtype=np.int64).reshape(-1)
+    if (pos < 0).any():
+        raise ValueError("a position is negative")
+    pos = np.minimum(pos, N.DOC_NONE)          # anything at or above n is "none"
+    count = int(pos.size)
+    doc = np.empty(max(count, 1), dtype=np.int64)
+    rel = np.empty(max(count, 1), dtype=np.int64)
+    if count:
+        N.require_device()
+    N.check(N.lib().sa_doc_of(off.ctypes.data, int(off.size) - 1, int(n), pos.ctypes.data if count else None, count, 8,
+                              doc.ctypes.data, rel.ctypes.data), "sa_doc_of")
+    doc, rel = doc[:count], rel[:count]
+    none = doc == N.DOC_NONE
+    doc[none] = -1
+    rel[none] = -1
+    return doc, rel
+
+
+def document_frequency(prev, lo, hi) -> np.ndarray:
+    """In how many documents each SA interval occurs, counted on the GPU
+    (sa_doc_frequency): int64, one entry per interval.  ``prev``: the second
+    array of document_array; ``lo`` / ``hi``: what find_patterns,
+    match_patterns or maximal_repeats return."""
+    p = _sa_array(prev)
+    lo, hi = _doc_intervals(lo, hi)
+    n, nq = int(p.size), int(lo.size)
+    df = np.zeros(max(nq, 1), dtype=np.uint64)
+    if n and nq:
+        N.require_device()
+    N.check(N.lib().sa_doc_frequency(p.ctypes.data if n else None, n, 8 if p.dtype == np.int64 else 4,
+                                     lo.ctypes.data if nq else None, hi.ctypes.data if nq else None, nq,
+                                     df.ctypes.data), "sa_doc_frequency")
+    return df[:nq].astype(np.int64)
+
+
+def list_documents(da, prev, lo, hi, max_docs: int = 0, order: str = "doc"):
+    """The distinct documents of a batch of SA intervals, listed on the GPU
+    (sa_doc_list), in CSR form.
+
+    ``da`` / ``prev``: what document_array returns.  Returns ``(offsets,
+    docs)``, both int64: interval q occurs in the documents
+    ``docs[offsets[q]:offsets[q + 1]]``, ascending, or in the order of their
+    first ranks with ``order="rank"``.  ``max_docs`` (0: no cap) keeps the
+    first ``max_docs`` documents in rank order (then sorted): not the smallest
+    ids."""
+    flags = _doc_order(order)
+    if max_docs < 0:
+        raise ValueError("max_docs is negative")
+    d, p = _sa_array(da), _sa_array(prev)
+    if d.size != p.size or d.dtype.itemsize != p.dtype.itemsize:
+        raise ValueError("da and prev: the same length and width")
+    lo, hi = _doc_intervals(lo, hi)
+    n, nq, width = int(d.size), int(lo.size), 8 if d.dtype == np.int64 else 4
+    off = np.zeros(nq + 1, dtype=np.uint64)
+    L = N.lib()
+
+    def call(out, cap):
+        N.check(L.sa_doc_list(d.ctypes.data if n else None, p.ctypes.data if n else None, n, width,
+                              lo.ctypes.data if nq else None, hi.ctypes.data if nq else None, nq, int(max_docs), flags,
+                              off.ctypes.data, out, cap), "sa_doc_list")
+
+    call(None, 0)                               # the host sizes the output from prev
+    total = int(off[nq])
+    docs = np.empty(max(total, 1), dtype=np.int64 if width == 8 else np.uint32)
+    if total:
+        N.require_device()
+        call(docs.ctypes.data, total)
+    return off.astype(np.int64), docs[:total].astype(np.int64)
+
+
 class SuffixArray:
     """The reference's SuffixArray object (suffix_array.h:16-21) driven
     through the drop-in C symbols of libsa_hip.so.
@@ -968,6 +1091,96 @@ class FMIndex:
         return off.astype(np.int64), pos[:total].astype(np.int64)
 
 
+class Collection:
+    """A collection of documents behind one suffix array built on the GPU.
+
+    The documents are concatenated, each followed by the one-byte
+    ``separator`` when one is given (it lies inside its document's range, so
+    a pattern without that byte never matches across two documents).  Without
+    a separator nothing is inserted and an occurrence belongs to the document
+    in which it starts.  The suffix array is built at once; the document
+    array and PRV on the first query that needs them.
+
+    >>> with Collection([b"abab", b"", b"ba"], separator=b"\\x00") as c:
+    ...     c.document_frequency([b"ab", b"ba"])     -> [1, 2]
+    """
+
+    def __init__(self, documents, separator=None):
+        parts = [_as_bytes_array(d).reshape(-1) for d in documents]
+        if not parts:
+            raise ValueError("a collection has at least one document")
+        if separator is not None:
+            sep = _as_bytes_array(separator).reshape(-1)
+            if sep.size != 1:
+                raise ValueError("separator: one byte")
+            parts = [np.concatenate([p, sep]) for p in parts]
+        self._off = np.zeros(len(parts) + 1, dtype=np.uint64)
+        self._off[1:] = np.cumsum([p.size for p in parts], dtype=np.uint64)
+        self._text = np.ascontiguousarray(np.concatenate(parts), dtype=np.uint8)
+        self.n = int(self._text.size)
+        self.D = len(parts)
+        self._sa = build_suffix_array(self._text) if self.n else np.zeros(0, dtype=np.uint32)
+        self._da = self._prev = None
+
+    def _docs(self):
+        if self._da is None:
+            self._da, self._prev = document_array(self._sa, self._off)
+        return self._da, self._prev
+
+    @property
+    def doc_offsets(self) -> np.ndarray:
+        """The D + 1 offsets of the documents in the concatenated text (int64)."""
+        return self._off.astype(np.int64)
+
+    @property
+    def text(self) -> bytes:
+        return self._text.tobytes()
+
+    @property
+    def sa(self) -> np.ndarray:
+        return self._sa.copy()
+
+    def find(self, patterns):
+        """(lo, hi) of each pattern in the collection's suffix array, as find_patterns gives them."""
+        return find_patterns(self._text, self._sa, patterns)
+
+    def count(self, patterns) -> np.ndarray:
+        """Occurrences of each pattern over all documents (int64)."""
+        lo, hi = self.find(patterns)
+        return hi - lo
+
+    def document_frequency(self, patterns) -> np.ndarray:
+        """In how many documents each pattern occurs (int64)."""
+        lo, hi = self.find(patterns)
+        return document_frequency(self._docs()[1], lo, hi)
+
+    def list_documents(self, patterns, max_docs: int = 0):
+        """``(offsets, docs)`` in CSR form: pattern q occurs in the documents
+        ``docs[offsets[q]:offsets[q + 1]]``, ascending (list_documents)."""
+        lo, hi = self.find(patterns)
+        da, prev = self._docs()
+        return list_documents(da, prev, lo, hi, max_docs)
+
+    def locate(self, patterns) -> list:
+        """Per pattern ``(doc, offset)``, two int64 arrays: its occurrences in
+        text order as (document, position inside the document)."""
+        lo, hi = self.find(patterns)
+        off, pos = locate_intervals(self._sa, lo, hi)
+        doc, rel = doc_of_positions(self._off, self.n, pos)
+        return [(doc[a:b], rel[a:b]) for a, b in zip(off[:-1].tolist(), off[1:].tolist())]
+
+    def close(self) -> None:
+        self._sa = np.zeros(0, dtype=np.uint32)
+        self._text = np.zeros(0, dtype=np.uint8)
+        self._da = self._prev = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
 class DeviceBuilder:
     """Device-resident builder: text and SA live in HBM (torch tensors or raw
     device pointers).  Holds one sa_context (workspace sized for max_n)."""
@@ -1165,6 +1378,49 @@ class DeviceBuilder:
                                         int(max_hits), _locate_flags(order, _chunks), self._ptr(d_off),
                                         None if d_pos is None else self._ptr(d_pos), int(pos_cap),
                                         ctypes.byref(total), s), "sa_locate_device")
+        return int(total.value)
+
+    def doc_array(self, n: int, d_sa, d_doc_off, D: int, d_da, d_prev=None, stream=None) -> None:
+        """Document array and PRV of a collection, everything in HBM
+        (sa_doc_array_device): d_sa n uint32, d_doc_off D + 1 uint64, d_da /
+        d_prev n uint32 each (either may be None, not both).  d_da alone is
+        only enqueued on ``stream``; with d_prev the call waits for it once
+        (the radix sort by document)."""
+        o = self._opt
+        N.check(self.L.sa_doc_array_device(self.ctx, n, o(d_sa), self._ptr(d_doc_off), int(D), o(d_da), o(d_prev),
+                                           _stream(stream)), "sa_doc_array_device")
+
+    def doc_of(self, d_doc_off, D: int, n: int, d_pos, count: int, d_doc, d_rel=None, stream=None) -> None:
+        """(document, offset inside it) of count uint32 positions, everything
+        in HBM (sa_doc_of_device): d_doc / d_rel count uint32 each (either may
+        be None, not both), N.DOC_NONE for a position that is not below n.
+        Enqueued on ``stream``; does not wait for it."""
+        o = self._opt
+        N.check(self.L.sa_doc_of_device(self._ptr(d_doc_off), int(D), n, o(d_pos), count, o(d_doc), o(d_rel),
+                                        _stream(stream)), "sa_doc_of_device")
+
+    def doc_frequency(self, n: int, d_prev, d_lo, d_hi, nq: int, d_df, stream=None) -> None:
+        """Document frequency of nq SA intervals, everything in HBM
+        (sa_doc_frequency_device): d_lo / d_hi (uint32) as find, match,
+        fm_count or repeats write them, d_df nq uint32.  Enqueued on
+        ``stream``; does not wait for it."""
+        o = self._opt
+        N.check(self.L.sa_doc_frequency_device(n, o(d_prev), o(d_lo), o(d_hi), nq, o(d_df), _stream(stream)),
+                "sa_doc_frequency_device")
+
+    def doc_list(self, n: int, d_da, d_prev, d_lo, d_hi, nq: int, d_off, d_docs, docs_cap: int, max_docs: int = 0,
+                 order: str = "doc", stream=None) -> int:
+        """The distinct documents of nq SA intervals in CSR form, everything in
+        HBM (sa_doc_list_device): d_off nq + 1 uint64, d_docs docs_cap uint32
+        at any 4-byte alignment.  Returns the total number of ids.  They are
+        written only when the total fits docs_cap and d_docs is not None: call
+        once with ``d_docs=None`` to size the output, allocate, and call
+        again.  Waits for ``stream``."""
+        o = self._opt
+        total = ctypes.c_uint64()
+        N.check(self.L.sa_doc_list_device(self.ctx, n, o(d_da), o(d_prev), o(d_lo), o(d_hi), nq, int(max_docs),
+                                          _doc_order(order), o(d_off), o(d_docs), int(docs_cap), ctypes.byref(total),
+                                          _stream(stream)), "sa_doc_list_device")
         return int(total.value)
 
     def mems(self, d_text, n: int, d_sa, d_query, m: int, min_len: int, d_off, d_tpos, d_len, out_cap: int,

@@ -2519,6 +2519,12 @@ static int scan_i64(int64_t* d_v, uint64_t m, hipStream_t s) {
 // hit lists sa_locate.h sorts
 #include "sa_fm.h"
 
+// document collections over one suffix array: the document array and the
+// previous-occurrence array (the context's radix sort), document frequency
+// of SA intervals in one filtered pass, document listing whose ids
+// sa_locate.h sorts
+#include "sa_docs.h"
+
 extern "C" {
 
 int sa_running_max_i64_device(int64_t* d_v, uint64_t m, void* stream) {

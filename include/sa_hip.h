@@ -559,6 +559,110 @@ int sa_locate_device(sa_context* ctx, uint64_t n, const uint32_t* d_sa, const ui
 int sa_locate(const void* sa, uint64_t n, int sa_width, const uint64_t* lo, const uint64_t* hi, uint64_t nq,
               uint64_t max_hits, uint32_t flags, uint64_t* off_out /* nq + 1 */, void* pos_out, uint64_t pos_cap);
 
+/* ---- collections: document array, document frequency and listing ---------
+ * (csrc/sa_docs.h).  A collection is a text of n bytes (n <= 2^32 - 1) and
+ * D + 1 non-decreasing uint64 offsets doc_off with doc_off[0] = 0 and
+ * doc_off[D] = n, 1 <= D <= 2^32 - 2.  Document d is the bytes
+ * [doc_off[d], doc_off[d + 1]); empty documents are allowed anywhere and own
+ * no position.  The library inserts no separator and reserves no byte; an
+ * occurrence belongs to the document in which it STARTS.  A caller who wants
+ * no match to span two documents ends each document with a byte the patterns
+ * do not contain (it lies inside its document's range).  With the suffix
+ * array SA of the text:
+ *   doc(p)  = the largest d with doc_off[d] <= p (never an empty document);
+ *   DA[r]   = doc(SA[r]);
+ *   PRV[r]  = 1 + the largest r' < r with DA[r'] == DA[r], 0 when there is
+ *             none: r is the first rank of its document inside [lo, hi)
+ *             exactly when PRV[r] <= lo;
+ *   df[q]   = #{ r in [lo[q], hi[q]) : PRV[r] <= lo[q] }, the number of
+ *             distinct documents of the interval (document frequency);
+ *   listing: c[q] = min(df[q], max_docs) (max_docs == 0: no cap), off[0] = 0,
+ *             off[q + 1] = off[q] + c[q], and docs[off[q] .. off[q + 1]) = the
+ *             DA[r] of the FIRST c[q] qualifying ranks in rank order, then
+ *             sorted ascending (sa_locate_device's cap rule: deterministic,
+ *             not the max_docs smallest ids).  With SA_DOC_RANK_ORDER the
+ *             sort is skipped.
+ * The intervals are what sa_find, sa_match, sa_fm_count and sa_repeats give.
+ * One that breaks lo <= hi <= n counts as empty, and no load leaves
+ * d_prev[0, n), d_da[0, n), d_lo[0, nq) or d_hi[0, nq) whatever those arrays
+ * hold.  An interval of up to SA_DOC_GROUP_MAX ranks is counted by a group of
+ * 16 lanes; a longer one is cut into chunks of SA_DOC_TILE ranks that
+ * workgroups share. */
+#define SA_DOC_NONE 0xFFFFFFFFu /* sa_doc_of: the position is not in the text */
+#define SA_DOC_RANK_ORDER 1u    /* sa_doc_list: ids in rank order, not sorted */
+#define SA_DOC_TILE 2048        /* ranks per chunk of a long interval */
+#define SA_DOC_GROUP_MAX 256    /* the longest interval one lane group counts */
+#define SA_DOC_LDS_DOCS 8192    /* up to this D the boundaries are searched in LDS, above it in global memory */
+
+/* DA into d_da and PRV into d_prev (n uint32 each, 4-byte aligned; either may
+ * be NULL, not both) from d_sa (n uint32) and d_doc_off (D + 1 uint64), all in
+ * device memory.  d_sa is not checked: an entry >= n is taken as n - 1.
+ * d_doc_off is read at [0, D) only, whatever it holds (the host form checks
+ * it in full).  DA alone is one pass and only enqueued on `stream` (no host
+ * wait).  PRV sorts the ranks by document with the context's radix sort
+ * (sa_sort_pairs_device over the key bits D needs) and scatters neighbours:
+ * one host wait, the sort's own, and 24 n bytes of stream-ordered
+ * temporaries; the context's workspace grows to n.
+ * Checked before any HIP call (SA_E_INVALID): a NULL ctx, d_doc_off or (n > 0)
+ * d_sa, both outputs NULL, n too large, D == 0 or D > 2^32 - 2, a misaligned
+ * output, an output that is the other output or an input. */
+int sa_doc_array_device(sa_context* ctx, uint64_t n, const uint32_t* d_sa, const uint64_t* d_doc_off, uint64_t D,
+                        uint32_t* d_da /* may be NULL */, uint32_t* d_prev /* may be NULL */, void* stream);
+/* doc(p) into d_doc and p - doc_off[doc(p)] into d_rel (count uint32 each;
+ * either may be NULL, not both) for the count positions at d_pos (uint32, what
+ * sa_locate_device returns).  A position >= n gives SA_DOC_NONE in both.
+ * Asynchronous: no context, no host wait, no temporaries.  The same checks as
+ * above without the context. */
+int sa_doc_of_device(const uint64_t* d_doc_off, uint64_t D, uint64_t n, const uint32_t* d_pos, uint64_t count,
+                     uint32_t* d_doc /* may be NULL */, uint32_t* d_rel /* may be NULL */, void* stream);
+/* df[q] (uint32) of nq intervals.  Asynchronous like sa_find_device: no
+ * context, no host wait; every d_df[q] is written by the call itself (the
+ * chunks of a long interval are added into a word the call has zeroed), so two
+ * calls in a row give the same numbers.  The work is the sum of the interval
+ * lengths at 4 bytes per rank; one stream-ordered temporary of 8 (nq + 1)
+ * bytes.  Checked before any HIP call: NULL pointers (nq > 0), n or nq too
+ * large, a misaligned d_df, d_df an input. */
+int sa_doc_frequency_device(uint64_t n, const uint32_t* d_prev, const uint32_t* d_lo, const uint32_t* d_hi, uint64_t nq,
+                            uint32_t* d_df, void* stream);
+/* The listing, with sa_locate_device's two-call contract: always fills
+ * d_off[0, nq] and *total; ids are written only when d_docs is not NULL and
+ * *total <= docs_cap (exactly d_docs[0, total), at any 4-byte alignment);
+ * otherwise the call returns SA_OK with *total set and touches nothing in
+ * d_docs: the sizing call.  The qualifying ids are materialised (4 bytes each,
+ * stream-ordered) and sorted per query by sa_locate_device's kernels, so sorted
+ * output needs total <= 2^32 - 1 (SA_E_INVALID otherwise: cap it with
+ * max_docs).  A long interval's ids are written by one workgroup.
+ * Synchronises `stream`: one host wait for the total; when ids are written,
+ * sa_locate_device's own over them (one, more when a query lists more than
+ * SA_LOCATE_TILE documents), or one at the end with SA_DOC_RANK_ORDER.
+ * Checked before any HIP call: a NULL ctx, total, d_off or (nq > 0) d_da,
+ * d_prev, d_lo, d_hi; n or nq too large; unknown flags; a misaligned d_off or
+ * d_docs; an output that is an input or the other output. */
+int sa_doc_list_device(sa_context* ctx, uint64_t n, const uint32_t* d_da, const uint32_t* d_prev, const uint32_t* d_lo,
+                       const uint32_t* d_hi, uint64_t nq, uint64_t max_docs, uint32_t flags, uint64_t* d_off /* nq + 1 */,
+                       uint32_t* d_docs /* may be NULL */, uint64_t docs_cap, uint64_t* total, void* stream);
+/* Host in, host out, over the staging of the other host forms; they allocate,
+ * use and free device buffers.  Arrays of ranks, positions and ids have the
+ * given width (4: uint32, 8: int64; SA_DOC_NONE stays 0xFFFFFFFF at width 8);
+ * lo, hi, off_out and df_out are uint64.  Checked in full before any device
+ * work, each with its own message (SA_E_INVALID): the width; NULL pointers;
+ * doc_off not starting at 0, decreasing or not ending at n; D == 0 or too
+ * large; an interval with lo > hi or hi > n; docs_cap below the total; a
+ * width-8 entry out of range; an output that is an input or another output.
+ * sa_doc_list fills off_out on the host from prev, as sa_locate does from the
+ * intervals; with docs_out NULL it stops there (the sizing call: the total is
+ * off_out[nq]).  n == 0 (sa_doc_array), count == 0, nq == 0 and a total of 0
+ * return SA_OK without a device. */
+int sa_doc_array(const void* sa, uint64_t n, int sa_width, const uint64_t* doc_off /* D + 1 */, uint64_t D,
+                 void* da_out /* may be NULL */, void* prev_out /* may be NULL */);
+int sa_doc_of(const uint64_t* doc_off /* D + 1 */, uint64_t D, uint64_t n, const void* pos, uint64_t count, int width,
+              void* doc_out /* may be NULL */, void* rel_out /* may be NULL */);
+int sa_doc_frequency(const void* prev, uint64_t n, int width, const uint64_t* lo, const uint64_t* hi, uint64_t nq,
+                     uint64_t* df_out);
+int sa_doc_list(const void* da, const void* prev, uint64_t n, int width, const uint64_t* lo, const uint64_t* hi,
+                uint64_t nq, uint64_t max_docs, uint32_t flags, uint64_t* off_out /* nq + 1 */, void* docs_out,
+                uint64_t docs_cap);
+
 /* ---- maximal exact matches of a query against the text -------------------
  * (csrc/sa_mem.h).  Text T of n bytes with its suffix array, query Q of m
  * bytes, min_len = L >= 1.  A MEM is a triple (i, p, l) with all of:
