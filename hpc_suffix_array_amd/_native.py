@@ -101,6 +101,16 @@ DOC_TILE = 2048
 DOC_GROUP_MAX = 256
 DOC_LDS_DOCS = 8192
 DOC_ORDERS = {"doc": 0, "rank": DOC_RANK_ORDER}
+# longest common extensions (include/sa_hip.h SA_LCE_*): the minimum of no rank
+# (-1 in the int64 arrays of the Python interface), the text bytes the position
+# forms compare before they ask ISA, LCP and the index (csrc/sa_lce.h
+# kLceProbe), the ranks per block and per superblock of the index (kLceBlock,
+# kLceSuper) and the bytes of its header
+LCE_NONE = 0xFFFFFFFF
+LCE_PROBE = 16
+LCE_BLOCK = 64
+LCE_SUPER = 4096
+LCE_HEADER = 4096
 
 # every symbol include/*.h declares
 DROPIN_SYMBOLS = ["create_suffix_array", "destroy_suffix_array", "build_suffix_array",
@@ -122,6 +132,8 @@ EXT_SYMBOLS = ["sa_context_create", "sa_context_destroy", "sa_context_set_debug"
                "sa_fm_build", "sa_fm_count", "sa_fm_locate",
                "sa_doc_array_device", "sa_doc_of_device", "sa_doc_frequency_device", "sa_doc_list_device",
                "sa_doc_array", "sa_doc_of", "sa_doc_frequency", "sa_doc_list",
+               "sa_lce_index_bytes", "sa_lce_build_device", "sa_lcp_min_device", "sa_lce_device",
+               "sa_substr_compare_device", "sa_lcp_min", "sa_lce", "sa_substr_compare",
                "sa_dist_begin", "sa_dist_cuts", "sa_dist_plan_cuts", "sa_dist_reserve", "sa_dist_release", "sa_dist_round1", "sa_dist_req_count", "sa_dist_req_fill",
                "sa_dist_answer", "sa_dist_refine",
                "sa_last_error", "sa_host_syncs", "sa_device_count", "sa_version", "sa_struct_size"]
@@ -397,6 +409,22 @@ def lib() -> ctypes.CDLL:
     L.sa_doc_frequency.restype = i32
     L.sa_doc_list.argtypes = [vp, vp, u64, i32, vp, vp, u64, u64, u32, vp, vp, u64]
     L.sa_doc_list.restype = i32
+    L.sa_lce_index_bytes.argtypes = [u64]
+    L.sa_lce_index_bytes.restype = u64
+    L.sa_lce_build_device.argtypes = [u64, vp, vp, u64, vp]
+    L.sa_lce_build_device.restype = i32
+    L.sa_lcp_min_device.argtypes = [u64, vp, vp, u64, vp, vp, u64, vp, vp]
+    L.sa_lcp_min_device.restype = i32
+    L.sa_lce_device.argtypes = [u64, vp, vp, vp, vp, u64, vp, vp, u64, vp, vp]
+    L.sa_lce_device.restype = i32
+    L.sa_substr_compare_device.argtypes = [u64, vp, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp]
+    L.sa_substr_compare_device.restype = i32
+    L.sa_lcp_min.argtypes = [vp, u64, i32, vp, vp, u64, vp]
+    L.sa_lcp_min.restype = i32
+    L.sa_lce.argtypes = [vp, u64, vp, i32, vp, vp, u64, vp]
+    L.sa_lce.restype = i32
+    L.sa_substr_compare.argtypes = [vp, u64, vp, i32, vp, vp, vp, vp, u64, vp]
+    L.sa_substr_compare.restype = i32
     DI =ctypes.POINTER(SaDistInfo)
     L.sa_dist_begin.argtypes = [vp, vp, u64, i32, i32, ctypes.POINTER(ctypes.c_uint32), vp, vp, DI]
     L.sa_dist_cuts.argtypes = [vp, ctypes.POINTER(u64), DI]

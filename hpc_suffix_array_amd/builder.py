@@ -824,6 +824,169 @@ def list_documents(da, prev, lo, hi, max_docs: int = 0, order: str = "doc"):
     return off.astype(np.int64), docs[:total].astype(np.int64)
 
 
+def _lce_queries(*arrays):
+    """Query arrays of one length as uint64 (negative entries rejected)."""
+    out = []
+    for a in arrays:
+        a = np.ascontiguousarray(a, dtype=np.int64).reshape(-1)
+        if (a < 0).any():
+            raise ValueError("a position, bound or length is negative")
+        out.append(a.astype(np.uint64))
+    if any(a.size != out[0].size for a in out):
+        raise ValueError("query arrays of different lengths: " + ", ".join(str(a.size) for a in out))
+    return out
+
+
+def _lce_none_to_minus_one(a: np.ndarray) -> np.ndarray:
+    a = a.astype(np.int64)
+    a[a == N.LCE_NONE] = -1
+    return a
+
+
+def lcp_range_min(lcp, lo, hi) -> np.ndarray:
+    """``min lcp[lo + 1 : hi]`` of a batch of SA intervals ``[lo, hi)`` on the
+    GPU (sa_lcp_min): the length of the longest common prefix of all suffixes
+    of the interval, its string depth.  ``lcp``: what lcp_array returns;
+    ``lo`` / ``hi``: what find_patterns, match_patterns, maximal_repeats or
+    FMIndex.find return.  int64, -1 where there is no minimum: an interval of
+    fewer than two ranks, or one that breaks ``lo < hi <= n``.  The index over
+    ``lcp`` is built for the call; LCEIndex keeps one."""
+    p = _sa_array(lcp)
+    lo, hi = _lce_queries(lo, hi)
+    n, nq = int(p.size), int(lo.size)
+    out = np.full(max(nq, 1), N.LCE_NONE, dtype=np.uint64)
+    if nq and ((hi <= n) & (lo < hi) & (hi - np.minimum(lo, hi) >= 2)).any():
+        N.require_device()
+    N.check(N.lib().sa_lcp_min(p.ctypes.data if n else None, n, 8 if p.dtype == np.int64 else 4,
+                               lo.ctypes.data if nq else None, hi.ctypes.data if nq else None, nq, out.ctypes.data),
+            "sa_lcp_min")
+    return _lce_none_to_minus_one(out[:nq])
+
+
+def _lce_host(t_ptr, n: int, sa_ptr, width: int, i, j) -> np.ndarray:
+    """sa_lce over host pointers: int64 lengths."""
+    i, j = _lce_queries(i, j)
+    nq = int(i.size)
+    out = np.zeros(max(nq, 1), dtype=np.uint64)
+    if n and nq:
+        N.require_device()
+    N.check(N.lib().sa_lce(t_ptr if n else None, n, sa_ptr if n else None, width, i.ctypes.data if nq else None,
+                           j.ctypes.data if nq else None, nq, out.ctypes.data), "sa_lce")
+    return out[:nq].astype(np.int64)
+
+
+def longest_common_extension(text, sa, i, j) -> np.ndarray:
+    """``lce(i, j)``, the length of the longest common prefix of the suffixes
+    at text positions ``i[q]`` and ``j[q]``, for a batch of pairs on the GPU
+    (sa_lce): int64.  A position at or past the end is the empty suffix (0);
+    ``lce(i, i) = n - i``.  LCP, the inverse suffix array and the index are
+    computed for the call from ``(text, sa)``; LCEIndex keeps them in HBM."""
+    t, s = _text_and_sa(text, sa)
+    return _lce_host(t.ctypes.data, int(t.size), s.ctypes.data, 8 if s.dtype == np.int64 else 4, i, j)
+
+
+def compare_substrings(text, sa, i, li, j, lj) -> np.ndarray:
+    """Order of the substrings ``text[i:i + li]`` and ``text[j:j + lj]``
+    (lengths clipped to the text's end) for a batch of pairs on the GPU
+    (sa_substr_compare): int8, -1, 0 or +1, what comparing the two bytes
+    objects gives."""
+    t, s = _text_and_sa(text, sa)
+    i, li, j, lj = _lce_queries(i, li, j, lj)
+    n, nq = int(t.size), int(i.size)
+    out = np.zeros(max(nq, 1), dtype=np.int8)
+    if n and nq:
+        N.require_device()
+    p = lambda a: a.ctypes.data if nq else None  # noqa: E731
+    N.check(N.lib().sa_substr_compare(t.ctypes.data if n else None, n, s.ctypes.data if n else None,
+                                      8 if s.dtype == np.int64 else 4, p(i), p(li), p(j), p(lj), nq, out.ctypes.data),
+            "sa_substr_compare")
+    return out[:nq]
+
+
+def _to_torch(a: np.ndarray):
+    """A numpy array as a host tensor (copied first when it is read-only: torch wants a writable one)."""
+    import torch
+    return torch.from_numpy(a if a.flags.writeable else a.copy())
+
+
+def _dev_ptr(x):
+    """The device address of a tensor (None for an empty one) or an int as it is."""
+    if x is None:
+        return None
+    if isinstance(x, int):
+        return x
+    return int(x.data_ptr()) if x.numel() else None
+
+
+def _dev_words(x, name: str):
+    """A contiguous device tensor of 32-bit entries."""
+    if not hasattr(x, "data_ptr") or x.element_size() != 4 or not x.is_contiguous():
+        raise ValueError(f"{name}: a contiguous device tensor of 32-bit entries")
+    return x
+
+
+def _lce_build_dev(L, lcp, stream=None):
+    import torch
+    lcp = _dev_words(lcp, "lcp")
+    n = int(lcp.numel())
+    nbytes = int(L.sa_lce_index_bytes(n))
+    index = torch.empty(nbytes, dtype=torch.uint8, device=lcp.device)
+    N.check(L.sa_lce_build_device(n, _dev_ptr(lcp), _dev_ptr(index), nbytes, _stream(stream)), "sa_lce_build_device")
+    return index
+
+
+def _lce_same_length(*qs):
+    if any(int(a.numel()) != int(qs[0].numel()) for a in qs):
+        raise ValueError("query tensors of different lengths: " + ", ".join(str(int(a.numel())) for a in qs))
+    return int(qs[0].numel())
+
+
+def _lce_out(out, nq: int, dtype, device):
+    """The output tensor of a query: the caller's (nq entries of dtype) or a new one."""
+    import torch
+    if out is None:
+        return torch.empty(nq, dtype=dtype, device=device)
+    if int(out.numel()) != nq or out.dtype != dtype or not out.is_contiguous():
+        raise ValueError(f"out: a contiguous {dtype} tensor of {nq} entries")
+    return out
+
+
+def _lcp_min_dev(L, lcp, index, lo, hi, index_bytes=None, stream=None, out=None):
+    import torch
+    lcp, lo, hi = _dev_words(lcp, "lcp"), _dev_words(lo, "lo"), _dev_words(hi, "hi")
+    nq = _lce_same_length(lo, hi)
+    out = _lce_out(out, nq, torch.int32, lo.device)
+    N.check(L.sa_lcp_min_device(int(lcp.numel()), _dev_ptr(lcp), _dev_ptr(index),
+                                int(index.numel()) if index_bytes is None else int(index_bytes), _dev_ptr(lo),
+                                _dev_ptr(hi), nq, _dev_ptr(out), _stream(stream)), "sa_lcp_min_device")
+    return out
+
+
+def _lce_dev(L, isa, lcp, index, i, j, text=None, lengths=None, index_bytes=None, stream=None, out=None):
+    """sa_lce_device, or sa_substr_compare_device with ``lengths = (li, lj)``."""
+    import torch
+    isa, lcp, i, j = _dev_words(isa, "isa"), _dev_words(lcp, "lcp"), _dev_words(i, "i"), _dev_words(j, "j")
+    n = int(lcp.numel())
+    if int(isa.numel()) != n or (text is not None and int(text.numel()) != n):
+        raise ValueError("text, isa and lcp: the same length")
+    if text is not None and (text.element_size() != 1 or not text.is_contiguous()):
+        raise ValueError("text: a contiguous device tensor of bytes")
+    ib = int(index.numel()) if index_bytes is None else int(index_bytes)
+    if lengths is None:
+        nq = _lce_same_length(i, j)
+        out = _lce_out(out, nq, torch.int32, i.device)
+        N.check(L.sa_lce_device(n, _dev_ptr(text), _dev_ptr(isa), _dev_ptr(lcp), _dev_ptr(index), ib, _dev_ptr(i),
+                                _dev_ptr(j), nq, _dev_ptr(out), _stream(stream)), "sa_lce_device")
+        return out
+    li, lj = _dev_words(lengths[0], "li"), _dev_words(lengths[1], "lj")
+    nq = _lce_same_length(i, li, j, lj)
+    out = _lce_out(out, nq, torch.int8, i.device)
+    N.check(L.sa_substr_compare_device(n, _dev_ptr(text), _dev_ptr(isa), _dev_ptr(lcp), _dev_ptr(index), ib, _dev_ptr(i),
+                                       _dev_ptr(li), _dev_ptr(j), _dev_ptr(lj), nq, _dev_ptr(out), _stream(stream)),
+            "sa_substr_compare_device")
+    return out
+
+
 class SuffixArray:
     """The reference's SuffixArray object (suffix_array.h:16-21) driven
     through the drop-in C symbols of libsa_hip.so.
@@ -921,6 +1084,13 @@ class SuffixArray:
         N.require_device()
         c = self.p.contents
         return _repeats_host(c.str, self.n, ctypes.cast(c.sa, ctypes.c_void_p).value, 4, min_len, min_occ, k)
+
+    def lce(self, i: int, j: int) -> int:
+        """Length of the longest common prefix of the suffixes at ``i`` and
+        ``j`` (sa_lce at width 4 over the object's own str / sa; build()
+        first).  The one-shot form: LCEIndex answers batches."""
+        c = self.p.contents
+        return int(_lce_host(c.str, self.n, ctypes.cast(c.sa, ctypes.c_void_p).value, 4, [i], [j])[0])
 
     def count(self, pattern) -> int:
         lo, hi = self.find(pattern)
@@ -1181,6 +1351,166 @@ class Collection:
         self.close()
 
 
+class LCEIndex:
+    """Longest common extensions of a text, answered on the GPU: the text, its
+    inverse suffix array, its LCP array, its suffix array and the range-minimum
+    index over LCP (sa_lce_build_device; about 0.4 n bytes) stay in HBM, and a
+    batch of queries is one kernel.
+
+    >>> with LCEIndex.from_text(b"abababc") as x:
+    ...     x.lce([0, 1], [2, 3])                   -> [4, 3]
+    ...     x.compare([0], [2], [2], [2])           -> [0]      (b"ab" == b"ab")
+    ...     x.interval_depth([0], [3])              -> [2]      (ranks 0 .. 2 share b"ab")
+    """
+
+    _MAGIC = b"SALCEBL1"
+
+    def __init__(self, text, isa, lcp, index, sa=None):
+        self.L = N.lib()
+        self.n = int(lcp.numel())
+        self._text, self._isa, self._lcp, self._index, self._sa = text, isa, lcp, index, sa
+
+    @staticmethod
+    def _padded(torch, nbytes: int, dtype, count: int):
+        """``count`` entries at the front of an allocation of at least nbytes bytes, zeroed."""
+        item = torch.empty(0, dtype=dtype).element_size()
+        return torch.zeros((nbytes + item - 1) // item + 64, dtype=dtype, device="cuda")[:count]
+
+    @classmethod
+    def _from_device_sa(cls, b, torch, d_text, n: int, d_sa) -> "LCEIndex":
+        d_lcp = cls._padded(torch, 4 * n, torch.int32, n)
+        d_isa = cls._padded(torch, 4 * n, torch.int32, n)
+        if n:
+            b.lcp(d_text, n, d_sa, d_lcp)
+            b.inverse(n, d_sa, d_isa)
+        return cls(d_text, d_isa, d_lcp, _lce_build_dev(b.L, d_lcp), d_sa)
+
+    @classmethod
+    def from_sa(cls, text, sa) -> "LCEIndex":
+        """From a text and its suffix array (checked on the GPU: SAError when it is not)."""
+        import torch
+        t, s = _text_and_sa(text, sa)
+        n = int(t.size)
+        N.require_device()
+        if n and s.dtype == np.int64:
+            if int(s.min()) < 0 or int(s.max()) >= n:
+                raise N.SAError("LCEIndex: SA entry out of range")
+        b = DeviceBuilder(max(n, 1))
+        try:
+            d_text = cls._padded(torch, n + 256, torch.uint8, n)
+            d_sa = cls._padded(torch, 4 * n, torch.int32, n)
+            if n:
+                d_text.copy_(_to_torch(t))
+                d_sa.copy_(_to_torch(s.astype(np.uint32).view(np.int32)))
+                if not b.check(d_text, n, d_sa):
+                    raise N.SAError("LCEIndex: not a valid suffix array of the text")
+            return cls._from_device_sa(b, torch, d_text, n, d_sa)
+        finally:
+            b.close()
+
+    @classmethod
+    def from_text(cls, text) -> "LCEIndex":
+        """Suffix array, LCP, inverse and index in one go, all on the GPU."""
+        import torch
+        t = _as_bytes_array(text).reshape(-1)
+        n = int(t.size)
+        N.require_device()
+        b = DeviceBuilder(max(n, 1))
+        try:
+            d_text = cls._padded(torch, n + 256, torch.uint8, n)
+            d_sa = cls._padded(torch, 4 * n, torch.int32, n)
+            if n:
+                d_text.copy_(_to_torch(t))
+                b.build(d_text, n, d_sa)
+            return cls._from_device_sa(b, torch, d_text, n, d_sa)
+        finally:
+            b.close()
+
+    @property
+    def nbytes(self) -> int:
+        """Bytes of the range-minimum index alone."""
+        return int(self._index.numel())
+
+    def _queries(self, *arrays):
+        import torch
+        qs = [np.minimum(a, np.uint64(0xFFFFFFFF)).astype(np.uint32).view(np.int32) for a in _lce_queries(*arrays)]
+        return [torch.from_numpy(a).to(self._lcp.device) for a in qs]
+
+    def _open(self):
+        if self._lcp is None:
+            raise N.SAError("the LCEIndex is closed")
+
+    def lce(self, i, j, probe: bool = True) -> np.ndarray:
+        """``lce(i[q], j[q])`` for a batch of position pairs: int64.  ``probe=False``
+        skips the comparison of the first bytes of the text; the answers are the same."""
+        self._open()
+        i, j = self._queries(i, j)
+        out = _lce_dev(self.L, self._isa, self._lcp, self._index, i, j, self._text if probe else None)
+        return out.cpu().numpy().view(np.uint32).astype(np.int64)
+
+    def compare(self, i, li, j, lj, probe: bool = True) -> np.ndarray:
+        """Order of ``text[i:i + li]`` and ``text[j:j + lj]`` for a batch: int8, -1, 0 or +1."""
+        self._open()
+        i, li, j, lj = self._queries(i, li, j, lj)
+        out = _lce_dev(self.L, self._isa, self._lcp, self._index, i, j, self._text if probe else None, (li, lj))
+        return out.cpu().numpy()
+
+    def interval_depth(self, lo, hi) -> np.ndarray:
+        """String depth of the SA intervals ``[lo, hi)``: the length of the
+        longest common prefix of their suffixes, ``n - sa[lo]`` for an
+        interval of one suffix; int64, -1 for an empty or broken interval."""
+        self._open()
+        lo64, hi64 = _lce_queries(lo, hi)
+        lo, hi = self._queries(lo64, hi64)
+        out = _lcp_min_dev(self.L, self._lcp, self._index, lo, hi)
+        depth = _lce_none_to_minus_one(out.cpu().numpy().view(np.uint32))
+        one = np.flatnonzero((lo64 < hi64) & (hi64 <= self.n) & (hi64 - np.minimum(lo64, hi64) == 1))
+        if one.size:
+            if self._sa is None:
+                raise N.SAError("the depth of a one-suffix interval needs the suffix array: build with from_sa or from_text")
+            import torch
+            at = torch.from_numpy(lo64[one].astype(np.int64)).to(self._sa.device)
+            depth[one] = self.n - self._sa[at].cpu().numpy().view(np.uint32).astype(np.int64)
+        return depth
+
+    def to_bytes(self) -> bytes:
+        """Everything the queries need as one byte string: text, ISA, LCP, SA and the index."""
+        self._open()
+        parts = [self._text, self._isa, self._lcp, self._index] + ([self._sa] if self._sa is not None else [])
+        head = self._MAGIC + np.array([self.n, self.nbytes, 0 if self._sa is None else 1], np.uint64).tobytes()
+        return head + b"".join(p.cpu().numpy().tobytes() for p in parts)
+
+    @classmethod
+    def from_bytes(cls, data) -> "LCEIndex":
+        import torch
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        if buf.size < 32 or bytes(buf[:8]) != cls._MAGIC:
+            raise N.SAError("not an LCE index: no header")
+        n, ib, has_sa = (int(x) for x in buf[8:32].view(np.uint64))
+        sizes = [n, 4 * n, 4 * n, ib] + ([4 * n] if has_sa else [])
+        if has_sa > 1 or ib != int(N.lib().sa_lce_index_bytes(n)) or buf.size != 32 + sum(sizes):
+            raise N.SAError(f"not an LCE index: {buf.size} bytes do not hold n = {n}")
+        N.require_device()
+        parts, at = [], 32
+        for k, size in enumerate(sizes):
+            dtype = torch.uint8 if k in (0, 3) else torch.int32
+            d = cls._padded(torch, size + 256, dtype, size // (1 if k in (0, 3) else 4))
+            if size:
+                d.copy_(torch.from_numpy(buf[at:at + size].copy().view(np.uint8 if k in (0, 3) else np.int32)))
+            parts.append(d)
+            at += size
+        return cls(*parts)
+
+    def close(self) -> None:
+        self._text = self._isa = self._lcp = self._index = self._sa = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
 class DeviceBuilder:
     """Device-resident builder: text and SA live in HBM (torch tensors or raw
     device pointers).  Holds one sa_context (workspace sized for max_n)."""
@@ -1422,6 +1752,42 @@ class DeviceBuilder:
                                           _doc_order(order), o(d_off), o(d_docs), int(docs_cap), ctypes.byref(total),
                                           _stream(stream)), "sa_doc_list_device")
         return int(total.value)
+
+    def lce_index_bytes(self, n: int) -> int:
+        """Bytes of the LCE index of n ranks (sa_lce_index_bytes): exact."""
+        return int(self.L.sa_lce_index_bytes(n))
+
+    def lce_build(self, lcp, stream=None):
+        """The range-minimum index over the LCP array in the device tensor
+        ``lcp`` (n 32-bit entries, 16-byte aligned, as ``lcp`` writes them), in
+        HBM (sa_lce_build_device): a new uint8 tensor of lce_index_bytes(n)
+        bytes.  Enqueued on ``stream``; does not wait for it."""
+        return _lce_build_dev(self.L, lcp, stream)
+
+    def lcp_min(self, lcp, index, lo, hi, stream=None, index_bytes=None, out=None):
+        """``min lcp[lo + 1 : hi]`` of the SA intervals in the device tensors
+        ``lo`` / ``hi`` (32-bit entries, as find, match, fm_count or repeats
+        write them), everything in HBM (sa_lcp_min_device): an int32 tensor
+        whose bits are uint32, N.LCE_NONE where there is no minimum (``out``,
+        or a new one).  Enqueued on ``stream``; does not wait for it."""
+        return _lcp_min_dev(self.L, lcp, index, lo, hi, index_bytes, stream, out)
+
+    def lce(self, isa, lcp, index, i, j, text=None, stream=None, index_bytes=None, out=None):
+        """``lce(i[q], j[q])`` of the text positions in the device tensors
+        ``i`` / ``j`` (32-bit entries), everything in HBM (sa_lce_device):
+        ``isa`` as ``inverse`` writes it, ``lcp`` as ``lcp`` does, ``index`` from
+        ``lce_build``; with ``text`` (the n bytes) the first N.LCE_PROBE bytes
+        are compared before the arrays are asked.  An int32 tensor whose bits
+        are uint32 (``out``, or a new one).  Enqueued on ``stream``; does not
+        wait for it."""
+        return _lce_dev(self.L, isa, lcp, index, i, j, text, None, index_bytes, stream, out)
+
+    def substr_compare(self, isa, lcp, index, i, li, j, lj, text=None, stream=None, index_bytes=None, out=None):
+        """Order of the substrings ``[i, i + li)`` and ``[j, j + lj)`` of the
+        text, everything in HBM (sa_substr_compare_device): an int8 tensor of
+        -1, 0, +1 (``out``, or a new one).  The arguments of ``lce`` plus the
+        two length tensors.  Enqueued on ``stream``; does not wait for it."""
+        return _lce_dev(self.L, isa, lcp, index, i, j, text, (li, lj), index_bytes, stream, out)
 
     def mems(self, d_text, n: int, d_sa, d_query, m: int, min_len: int, d_off, d_tpos, d_len, out_cap: int,
              max_occ: int = 0, max_candidates: int = 0, mode: str = "auto", stream=None) -> tuple:

@@ -2525,6 +2525,12 @@ static int scan_i64(int64_t* d_v, uint64_t m, hipStream_t s) {
 // sa_locate.h sorts
 #include "sa_docs.h"
 
+// longest common extensions: a range-minimum index over the LCP array (block
+// minima, a sparse table inside each superblock and one over the
+// superblocks), rank-interval minima, LCE of two positions and substring
+// order, all by one query kernel
+#include "sa_lce.h"
+
 extern "C" {
 
 int sa_running_max_i64_device(int64_t* d_v, uint64_t m, void* stream) {

@@ -663,6 +663,81 @@ int sa_doc_list(const void* da, const void* prev, uint64_t n, int width, const u
                 uint64_t nq, uint64_t max_docs, uint32_t flags, uint64_t* off_out /* nq + 1 */, void* docs_out,
                 uint64_t docs_cap);
 
+/* ---- longest common extensions: an RMQ index over the LCP array ------------
+ * (csrc/sa_lce.h).  LCP as sa_lcp_device writes it: lcp[0] = 0, lcp[r] =
+ * lcp(SA[r - 1], SA[r]), n <= 2^32 - 1.  SA_LCE_NONE is the minimum's identity.
+ *   lcp_min(lo, hi) of an SA interval [lo, hi) = min lcp[lo + 1 .. hi - 1]: the
+ *             length of the longest common prefix of all suffixes of the
+ *             interval, its string depth (what find, match, fm_count and
+ *             repeats return intervals of).  The empty minimum (hi - lo <= 1)
+ *             is SA_LCE_NONE, and so is an interval that breaks lo < hi <= n.
+ *   lce(i, j) of two text positions, ISA the inverse suffix array: a position
+ *             >= n is the empty suffix and lce = 0 when either is one;
+ *             lce(i, i) = n - i; otherwise, with a = min(ISA[i], ISA[j]) and
+ *             b = max(ISA[i], ISA[j]), lce(i, j) = min lcp[a + 1 .. b].
+ *   order     of the substrings T[i, i + li) and T[j, j + lj), lengths clipped
+ *             to the text's end: with l = min(lce(i, j), li, lj), sign(li - lj)
+ *             when l == min(li, lj), otherwise -1 when ISA[i] < ISA[j], else
+ *             +1; int8 in {-1, 0, +1}.  No text byte is needed.
+ * The index is one flat byte buffer of sa_lce_index_bytes(n) bytes that holds
+ * offsets and never pointers (16-byte aligned, copyable between devices and
+ * to a file): a 4096-byte header (magic, version, n, section offsets), the
+ * minima of the blocks of SA_LCE_BLOCK ranks with a sparse table over spans of
+ * 1 .. 32 blocks inside each superblock of SA_LCE_SUPER ranks, and a full
+ * sparse table over the superblock minima: 4096 + 4 (6 nb + levels ns) bytes
+ * rounded up to 16, nb = ceil(n / 64), ns = ceil(nb / 64), levels =
+ * floor(log2 ns) + 1 (under 0.40 n + 8 KiB for n >= 2^20).  The build reads
+ * LCP once, needs no context and no temporaries and makes no host wait; the
+ * header is written last.  n == 0 builds a valid empty index.
+ * A query is answered by 16 lanes: two masked blocks of LCP and at most six
+ * cells of the tables, all loaded at once (one memory round trip for a rank
+ * interval, two for a pair of positions: the ISA gathers first).  With d_text
+ * not NULL the position forms first compare SA_LCE_PROBE bytes at i and j and
+ * answer from them when the mismatch lies inside; the answers are the same
+ * with and without the text.  The kernel checks the header (magic, version,
+ * n, every section inside index_bytes): where it does not hold every query
+ * answers SA_LCE_NONE (order 0).  Ranks read from d_isa are clamped below n
+ * and cells to their section: whatever the arrays hold, no load leaves them.
+ * The queries make no host wait and use no temporaries.
+ * Rejected before any HIP call, each with its own message (SA_E_INVALID): n or
+ * nq above 2^32 - 1; a NULL pointer (d_text may be NULL; d_lcp and d_isa when
+ * n == 0); d_index or d_lcp not 16-byte aligned, d_out / d_lce not 4-byte
+ * aligned; index_bytes below sa_lce_index_bytes(n) at the build; an output
+ * that is an input.  nq == 0 is SA_OK without a launch. */
+#define SA_LCE_NONE 0xFFFFFFFFu /* the minimum of no rank */
+#define SA_LCE_PROBE 16         /* text bytes compared before ISA, LCP and the index are asked */
+#define SA_LCE_BLOCK 64         /* ranks per block */
+#define SA_LCE_SUPER 4096       /* ranks per superblock */
+/* pure host arithmetic, exact; 0 for n above 2^32 - 1 */
+uint64_t sa_lce_index_bytes(uint64_t n);
+int sa_lce_build_device(uint64_t n, const uint32_t* d_lcp, void* d_index, uint64_t index_bytes, void* stream);
+int sa_lcp_min_device(uint64_t n, const uint32_t* d_lcp, const void* d_index, uint64_t index_bytes,
+                      const uint32_t* d_lo, const uint32_t* d_hi, uint64_t nq, uint32_t* d_out, void* stream);
+int sa_lce_device(uint64_t n, const uint8_t* d_text /* or NULL */, const uint32_t* d_isa, const uint32_t* d_lcp,
+                  const void* d_index, uint64_t index_bytes, const uint32_t* d_i, const uint32_t* d_j, uint64_t nq,
+                  uint32_t* d_lce, void* stream);
+int sa_substr_compare_device(uint64_t n, const uint8_t* d_text /* or NULL */, const uint32_t* d_isa,
+                             const uint32_t* d_lcp, const void* d_index, uint64_t index_bytes, const uint32_t* d_i,
+                             const uint32_t* d_li, const uint32_t* d_j, const uint32_t* d_lj, uint64_t nq,
+                             int8_t* d_order, void* stream);
+/* Host in, host out, over the staging of the other host forms; they allocate,
+ * use and free device buffers.  lcp and sa have the given width (4: uint32,
+ * 8: int64); lo, hi, i, j, li, lj and the uint32 answers are uint64 (SA_LCE_NONE
+ * stays 0xFFFFFFFF), the order int8.  sa_lcp_min builds the index of lcp;
+ * sa_lce and sa_substr_compare compute LCP, ISA and the index from (text, sa)
+ * (sa must be the suffix array of the text) and probe the text.  A position
+ * or length above 2^32 - 1 counts as 2^32 - 1.  Checked before any device
+ * work (SA_E_INVALID): the width; n or nq too large; NULL pointers; a width-8
+ * entry out of range; an output that is an input.  nq == 0, n == 0 (the
+ * position forms) and a batch without any interval of two or more ranks
+ * return SA_OK without a device. */
+int sa_lcp_min(const void* lcp, uint64_t n, int width, const uint64_t* lo, const uint64_t* hi, uint64_t nq,
+               uint64_t* out);
+int sa_lce(const uint8_t* text, uint64_t n, const void* sa, int sa_width, const uint64_t* i, const uint64_t* j,
+           uint64_t nq, uint64_t* out);
+int sa_substr_compare(const uint8_t* text, uint64_t n, const void* sa, int sa_width, const uint64_t* i,
+                      const uint64_t* li, const uint64_t* j, const uint64_t* lj, uint64_t nq, int8_t* out);
+
 /* ---- maximal exact matches of a query against the text -------------------
  * (csrc/sa_mem.h).  Text T of n bytes with its suffix array, query Q of m
  * bytes, min_len = L >= 1.  A MEM is a triple (i, p, l) with all of:
