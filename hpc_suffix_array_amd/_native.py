@@ -149,7 +149,8 @@ DEBUG_FLAGS = {"no_cmp": 0x1, "no_pk8": 0x2, "no_pad": 0x4, "pad_overflow": 0x8,
                "no_pivot": 0x20, "perm_always": 0x40, "no_xq": 0x80, "xq_overflow": 0x100,
                "no_tied": 0x200, "no_key1_round": 0x400, "no_eonly": 0x800,
                "eonly": 0x1000, "fast32_small": 0x2000, "no_round2_fused": 0x4000,
-               "ls_one_wg": 0x8000, "no_alpha_sample": 0x10000, "alpha_sample_small": 0x20000}
+               "ls_one_wg": 0x8000, "no_alpha_sample": 0x10000, "alpha_sample_small": 0x20000,
+               "bb17": 0x40000, "bb18": 0x80000}
 
 
 def debug_bits(names) -> int:
@@ -218,6 +219,8 @@ class SaStats(ctypes.Structure):
                                 4: "striped-records-overflow"}.get(self.round1_segments, "exact"),
             "round1_layout": {"compact": bool(self.round1_layout & 1), "pk8": bool(self.round1_layout & 2),
                               "xq": bool(self.round1_layout & 4), "eonly": bool(self.round1_layout & 8)},
+            # bucketed round 1: digit bits of the second bucket pass (bucket bits - 8 on one GPU)
+            "round1_hb": (self.round1_layout >> 4) & 15,
             "reference_model_bytes": int(self.model_bytes),
             "round_bytes": [int(x) for x in self.round_bytes[:r]],
             # bucketed round 1: non-empty windows, one-bucket windows of the fixed-span kernel, windows

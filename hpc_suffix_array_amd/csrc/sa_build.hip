@@ -1482,9 +1482,11 @@ static int build_packed(sa_context* c, const uint8_t* d_text, uint64_t n, uint32
         // sort and the per-XCD second pass (1 GiB alnum: K 8 -> 7, 16.05 -> 13.59
         // ms, profiles/r06_h_bench_alnum_k*.log; DNA, ascii127, byte256: the same K)
         Kb = (opts && opts->init_chars > 0) || sigma <= 1 ? K : min_chars(sigma, n);
-        bucketed = plan_bucketed(sigma, n, Kb, r1, c->radix, &bp, 1, (c->dbg & SA_DEBUG_NO_CMP) ? 0 : 1);
+        // (tests: SA_DEBUG_BB17 / _BB18 widen the buckets of a small text; 0 in production)
+        const uint32_t bbf = (c->dbg & SA_DEBUG_BB18) ? 18u : (c->dbg & SA_DEBUG_BB17) ? 17u : 0u;
+        bucketed = plan_bucketed(sigma, n, Kb, r1, c->radix, &bp, 1, (c->dbg & SA_DEBUG_NO_CMP) ? 0 : 1, bbf);
         if (bucketed && bp.bs.cmp && short_suffix_ties(h_tail, n, tail_n, h_code, sigma, bp.bs.s, bp.bs.R))
-            bucketed = plan_bucketed(sigma, n, Kb, r1, c->radix, &bp, 1, 0);
+            bucketed = plan_bucketed(sigma, n, Kb, r1, c->radix, &bp, 1, 0, bbf);
         // a non-power-of-two alphabet one bit short of packed first-pass items
         // (1 GiB alnum / ascii127: 65 bits) takes the E-only layout when the
         // text's last K suffixes pad apart (BucketSpec, sa_kernels.h)
@@ -1493,7 +1495,7 @@ static int build_packed(sa_context* c, const uint8_t* d_text, uint64_t n, uint32
             !(c->dbg & SA_DEBUG_NO_EONLY)) {
             const uint32_t hb = bp.bs.bb - kLoBits;
             BucketPlan b2;
-            if ((force_eonly || !plan_pk8(bp, hb, c->dbg, true)) && plan_bucketed(sigma, n, Kb, r1, c->radix, &b2, 1, 2) &&
+            if ((force_eonly || !plan_pk8(bp, hb, c->dbg, true)) && plan_bucketed(sigma, n, Kb, r1, c->radix, &b2, 1, 2, bbf) &&
                 (force_eonly || plan_pk8(b2, hb, c->dbg, true)) &&
                 !short_suffix_ties(h_tail, n, tail_n, h_code, sigma, b2.bs.s, b2.bs.R, b2.K))
                 bp = b2;

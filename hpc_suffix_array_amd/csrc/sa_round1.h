@@ -121,8 +121,11 @@ struct BucketPlan {
 // build 2^bb / world of them.
 // cmp: the compact low of BucketSpec (only when short_suffix_ties is false
 // for the text)
+// bb_min (one GPU; tests: SA_DEBUG_BB17 / _BB18): bucket bits the plan takes when the size
+// alone gives fewer (17 or 18; 0: the size decides) -- the second pass's 9-
+// and 10-bit digits at sizes a CPU oracle sorts.  Never lowers bb.
 static bool plan_bucketed(uint32_t sigma, uint64_t n, uint32_t K, int round1, int radix, BucketPlan* p,
-                          int world = 1, int cmp = 0) {
+                          int world = 1, int cmp = 0, uint32_t bb_min = 0) {
     if (round1 == SA_ROUND1_LSD || radix != 0 || sigma < 2 || n < 2) return false;
     if (round1 == SA_ROUND1_AUTO && n < kBucketMinN) return false;
     // bucket bits: windows of about n / 2^bb suffixes must fit the
@@ -131,6 +134,7 @@ static bool plan_bucketed(uint32_t sigma, uint64_t n, uint32_t K, int round1, in
     uint32_t bb = std::max<uint32_t>(16u, bit_width(n - 1) > 13 ? bit_width(n - 1) - 13 : 0u);
     if (world <= 1) bb = std::min<uint32_t>(bb, 18u);
     bb += SA_BB_EXTRA;
+    if (world <= 1 && bb_min > bb) bb = std::min<uint32_t>(bb_min, 18u);
     if (bb > 18 + (uint32_t)bit_width((uint64_t)std::max(world, 1) - 1) || bb > 24) return false;
     uint64_t ps = 1;   // sigma^s >= 2^bb: the bb-bit bucket is dense
     uint32_t s = 0;
@@ -448,7 +452,9 @@ static int round1_bucketed(sa_context* c, const uint8_t* d_text, uint64_t n, uin
     static_assert(kXqQueues == kXq && kXqRegionSlack == kXqSlack, "sa_limits.h mirrors sa_split.h");
     const bool xq = SA_SEG_XQ && allow_xq && fast32 && c->cus % (int)kXq == 0 && !(c->dbg & SA_DEBUG_NO_XQ) &&
                     c->kucap >= xq_region_space(m) + kWave && xq_offsets_fit(m);   // (+ a row: load_items_cr)
-    if (st) st->round1_layout = (bp.bs.cmp ? 1 : 0) | (pk8 ? 2 : 0) | (xq ? 4 : 0) | (bp.bs.cmp == 2 ? 8 : 0);
+    if (st)
+        st->round1_layout = (bp.bs.cmp ? 1 : 0) | (pk8 ? 2 : 0) | (xq ? 4 : 0) | (bp.bs.cmp == 2 ? 8 : 0) |
+                            (int32_t)(hb << 4);   // bits 4-7: the second pass's digit bits
     // XQ workspace: queue cursors / bases / claim counts / tickets, the digit
     // sub-region starts, the per-region chunk starts and counts per bucket
     const uint64_t xqw = xq_words(1u << hb);

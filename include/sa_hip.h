@@ -114,6 +114,12 @@ enum sa_kernel_kind {
                                            blocks pays a wasted first and second pass before the exact re-run) */
 #define SA_DEBUG_ALPHA_SAMPLE_SMALL 0x20000u /* the sampled alphabet at any n, its sample the text's first 4096 bytes
                                            only (tests: both outcomes at sizes an oracle sorts) */
+#define SA_DEBUG_BB17 0x40000u          /* bucketed round 1 on one GPU: at least 17 bucket bits, whatever the size
+                                           (tests: the second bucket pass's 9-bit digit, which production takes
+                                           from 2^29 suffixes, at sizes an oracle sorts; never fewer bits than
+                                           the size gives; the range-partitioned build ignores it) */
+#define SA_DEBUG_BB18 0x80000u          /* the same with 18 bucket bits (the 10-bit digit: production from 2^30
+                                           suffixes); wins over SA_DEBUG_BB17 when both are set */
 
 /* sa_stats.alphabet */
 #define SA_ALPHABET_EXACT 0    /* from a pass over the whole text */
@@ -170,7 +176,9 @@ typedef struct {
     int32_t round1_layout;               /* bucketed round 1: bit 0 compact key1 low (BucketSpec.cmp),
                                             bit 1 packed 8-byte first-pass items (PK8), bit 2 the second
                                             pass by per-XCD queues and regions (XQ), bit 3 the E-only
-                                            key1 low (no end bit; non-power-of-two alphabets' PK8) */
+                                            key1 low (no end bit; non-power-of-two alphabets' PK8),
+                                            bits 4-7 the second pass's digit bits hb (7..10; bucket bits - 8
+                                            on one GPU) */
     uint64_t round_bytes[SA_MAX_ROUNDS]; /* algorithmic bytes of the kernels launched in round j (the kern_bytes
                                             added between its boundaries; the schedule actually run) */
     int32_t round1_windows[4];           /* bucketed round 1, the local sort's first launch: [0] non-empty windows,

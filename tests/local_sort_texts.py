@@ -31,6 +31,13 @@ k_window_starts_tab / k_window_list / k_window_split in numpy: bucket sizes,
 ws / wb, the one-bucket windows, their sizes, each one's largest sub-bucket
 (the top kSubBits bits of the bits1-bit bucket-relative key) and the tie
 groups.  Everything here runs without a GPU.
+
+The last section models the second bucket pass (sa_split.h k_split_seg) for
+tests/test_gpu_second_pass.py: host_plan / plan_bucketed take the bucket bits
+that debug bb17 / bb18 force, second_pass_units() restates the pass's unit
+numbering, the units' queues and k_xq_dh's sub-regions, and sp_text() builds
+the texts whose segments reach the pass's edges
+(tests/test_second_pass_texts.py asserts that on the CPU).
 """
 import functools
 
@@ -76,12 +83,13 @@ def min_chars(sigma, n):
     return k
 
 
-def plan_bucketed(sigma, n, K, cmp=1):
-    """BucketPlan of one GPU (world 1) as a dict, or None."""
+def plan_bucketed(sigma, n, K, cmp=1, bb=None):
+    """BucketPlan of one GPU (world 1) as a dict, or None.  bb: the bucket
+    bits debug bb17 / bb18 force (never fewer than the size gives)."""
     if sigma < 2 or n < 2:
         return None
     ib = (n - 1).bit_length()
-    bb = min(max(16, ib - 13 if ib > 13 else 0), 18)
+    bb = max(min(max(16, ib - 13 if ib > 13 else 0), 18), min(bb or 0, 18))
     ps, s = 1, 0
     while ps < (1 << bb):
         ps *= sigma
@@ -136,6 +144,46 @@ def bucket_dmin(b, cmul, bsh):
     return np.where(((d0 * np.uint64(cmul)) >> np.uint64(bsh)) == b, d0, d0 + np.uint64(1))
 
 
+def _dense_digits(text):
+    """(n, sigma, the text as dense digits 0 .. sigma - 1)."""
+    t = np.ascontiguousarray(text, dtype=np.uint8)
+    present = np.zeros(256, bool)
+    present[np.unique(t)] = True
+    return int(t.size), int(present.sum()), (np.cumsum(present) - 1)[t].astype(np.uint64)
+
+
+def host_plan(sigma, n, tail, init_chars=0, eonly=False, bb=None, no_cmp=False):
+    """The plan build_packed (sa_build.hip plan_round1) settles on with
+    round1="bucketed": the compact layout, the original one when the text's
+    tail ties (or debug no_cmp), the E-only one for a non-power-of-two
+    alphabet that packs only without the end bit (or debug eonly).  tail: the
+    text's last K_MAX_K dense digits.  None: no bucketed plan (round 1 is the
+    LSD sort)."""
+    K = init_chars if init_chars > 0 else min_chars(sigma, n)
+    p = plan_bucketed(sigma, n, K, 0 if no_cmp else 1, bb)
+    if p is None:
+        return None
+    if p["cmp"] and _short_suffix_ties(tail, p["s"], p["R"]):
+        p = plan_bucketed(sigma, n, K, 0, bb)
+        if p is None:
+            return None
+    np2 = (sigma & (sigma - 1)) != 0
+    if p["cmp"] == 1 and (np2 or eonly):
+        p2 = plan_bucketed(sigma, n, K, 2, bb)
+        if ((eonly or not _plan_pk8(p)) and p2 is not None and (eonly or _plan_pk8(p2))
+                and not _short_suffix_ties(tail, p2["s"], p2["R"], p2["K"])):
+            p = p2
+    return p
+
+
+def text_plan(text, init_chars=0, eonly=False, bb=None, no_cmp=False):
+    """host_plan of a text, with "pk8": whether plan_pk8 packs its first-pass
+    items (one GPU, no debug no_pk8)."""
+    n, sigma, dig = _dense_digits(text)
+    p = host_plan(sigma, n, dig[-K_MAX_K:], init_chars, eonly, bb, no_cmp)
+    return None if p is None else dict(p, pk8=_plan_pk8(p))
+
+
 # --------------------------------------------------------------------------
 # the window model
 # --------------------------------------------------------------------------
@@ -143,28 +191,13 @@ class WindowModel:
     """The bucketed first round of `text` at init_chars (0: auto) on one GPU,
     forced (round1="bucketed") with debug fast32_small: the layout the host
     picks (compact, E-only with `eonly`, the original one when the text's tail
-    ties), the windows and where k_window_split sends them."""
+    ties), the windows and where k_window_split sends them.  bb: the bucket
+    bits forced by debug bb17 / bb18."""
 
-    def __init__(self, text, init_chars=0, eonly=False):
-        t = np.ascontiguousarray(text, dtype=np.uint8)
-        n = int(t.size)
-        present = np.zeros(256, bool)
-        present[np.unique(t)] = True
-        sigma = int(present.sum())
-        dig_of = np.cumsum(present) - 1
-        dig = dig_of[t].astype(np.uint64)
-        K = init_chars if init_chars > 0 else min_chars(sigma, n)
-        p = plan_bucketed(sigma, n, K, 1)
-        assert p is not None, (sigma, n, K)
-        tail = dig[-K_MAX_K:]
-        if _short_suffix_ties(tail, p["s"], p["R"]):
-            p = plan_bucketed(sigma, n, K, 0)
-        np2 = (sigma & (sigma - 1)) != 0
-        if p["cmp"] == 1 and (np2 or eonly):
-            p2 = plan_bucketed(sigma, n, K, 2)
-            if ((eonly or not _plan_pk8(p)) and p2 is not None and (eonly or _plan_pk8(p2))
-                    and not _short_suffix_ties(tail, p2["s"], p2["R"], p2["K"])):
-                p = p2
+    def __init__(self, text, init_chars=0, eonly=False, bb=None):
+        n, sigma, dig = _dense_digits(text)
+        p = host_plan(sigma, n, dig[-K_MAX_K:], init_chars, eonly, bb)
+        assert p is not None, (sigma, n, init_chars, bb)
         self.plan, self.n, self.sigma = p, n, sigma
         s, R, rb, sg = p["s"], p["R"], p["rb"], np.uint64(sigma)
         assert sigma ** R < 2 ** 62 and p["ps"] <= 2 ** 32
@@ -442,5 +475,166 @@ DNA_TEXTS = ("dna_sparse", "dna_dense")
 
 
 @functools.lru_cache(maxsize=None)
-def model(name, init_chars=0, eonly=False):
-    return WindowModel(text(name), init_chars, eonly)
+def model(name, init_chars=0, eonly=False, bb=None):
+    return WindowModel(text(name), init_chars, eonly, bb)
+
+
+# --------------------------------------------------------------------------
+# the second bucket pass (sa_split.h k_split_seg): its work units, and the
+# texts of tests/test_gpu_second_pass.py; their coverage is asserted on the
+# CPU by tests/test_second_pass_texts.py
+# --------------------------------------------------------------------------
+K_LO_BITS = 8           # sa_bucket.h kLoBits: the first pass's digit
+K_SEGS = 1 << K_LO_BITS
+K_XQ = 8                # per-XCD queues (sa_bucket.h kXq)
+K_XQ_SLACK = 2048       # sa_split.h kXqSlack
+UNIT_PK = 12 * 1024     # SA_ITEMS_PK x 1024 threads: packed 8-byte items
+UNIT_B = 10 * 1024      # SA_ITEMS_B x 1024: 12-byte items
+
+
+class SecondPassUnits:
+    """What second_pass_units() returns:
+    seg_sizes[256]      items of segment l = bucket & 255 (the pass's input order)
+    digit_tot[2^hb]     items of high digit h = bucket >> 8
+    count[2^hb, 256]    items of bucket (h, l)
+    seg_units[256]      ceil(size / unit) units of segment l
+    unit_seg[U]         the segment of unit u: units are numbered segment by
+                        segment, empty segments take none (k_split_seg s_ubase)
+    unit_size[U]        its items (a segment's last unit holds the rest)
+    unit_queue[U]       u mod 8, the per-XCD queue that takes it
+    owns[8, 256]        queue q takes at least one unit of segment l
+    ub[8, 2^hb]         sum of count(h, l) over the segments q owns: an upper
+                        bound of q's share of digit h, exact where every
+                        segment is one unit
+    cap[2^hb]           k_xq_dh's sub-region of one queue's digit h"""
+
+    def __init__(self, bucket, bb, unit):
+        hb = bb - K_LO_BITS
+        self.bb, self.hb, self.unit = bb, hb, unit
+        b = np.asarray(bucket, dtype=np.int64)
+        assert int(b.max()) < (1 << bb)
+        self.count = np.bincount(b, minlength=1 << bb).reshape(1 << hb, K_SEGS)
+        self.seg_sizes = self.count.sum(axis=0)
+        self.digit_tot = self.count.sum(axis=1)
+        self.seg_units = -(-self.seg_sizes // unit)
+        self.unit_seg = np.repeat(np.arange(K_SEGS), self.seg_units)
+        first = np.cumsum(self.seg_units) - self.seg_units          # s_ubase
+        within = np.arange(len(self.unit_seg)) - first[self.unit_seg]
+        self.unit_size = np.minimum(self.seg_sizes[self.unit_seg] - within * unit, unit)
+        self.unit_queue = np.arange(len(self.unit_seg)) % K_XQ
+        self.owns = np.zeros((K_XQ, K_SEGS), bool)
+        self.owns[self.unit_queue, self.unit_seg] = True
+        self.ub = self.owns.astype(np.int64) @ self.count.T
+        self.cap = self.digit_tot // K_XQ + self.digit_tot // 128 + K_XQ_SLACK
+
+    @property
+    def last_unit(self):
+        """Items of each non-empty segment's last unit."""
+        sz = self.seg_sizes[self.seg_sizes > 0]
+        return sz - (-(-sz // self.unit) - 1) * self.unit
+
+    def summary(self):
+        sz = self.seg_sizes
+        return dict(bb=self.bb, unit=self.unit, units=len(self.unit_seg), seg_min=int(sz.min()), seg_max=int(sz.max()),
+                    empty_segs=int((sz == 0).sum()), empty_digits=int((self.digit_tot == 0).sum()),
+                    two_unit=int((self.seg_units == 2).sum()),
+                    short_last=int(((self.last_unit >= 1) & (self.last_unit <= 63)).sum()),
+                    ub_over_cap=float((self.ub / self.cap).max()))
+
+
+def second_pass_buckets(text, bb):
+    """bucket = (D cmul) >> bsh of every suffix under the auto plan at `bb`
+    bucket bits (D: the first s dense digits, digit 0 past the end; the bucket
+    depends on s and cmul only, not on the key1 low's layout)."""
+    n, sigma, dig = _dense_digits(text)
+    p = host_plan(sigma, n, dig[-K_MAX_K:], bb=bb)
+    assert p is not None and p["bb"] == bb, (sigma, n, bb, p)
+    pad = np.concatenate([dig, np.zeros(p["s"], np.uint64)])
+    D = np.zeros(n, np.uint64)
+    for q in range(p["s"]):
+        D = D * np.uint64(sigma) + pad[q:q + n]
+    return (D * np.uint64(p["cmul"])) >> np.uint64(p["bsh"])
+
+
+def second_pass_units(text, bb, unit):
+    return SecondPassUnits(second_pass_buckets(text, bb), bb, unit)
+
+
+SP_N = 3 << 20
+# the TT-free text: at 3 x 2^20 nearly all of its 216 non-empty segments are
+# two units (one full, one small), a queue owns a unit of ~52 of them, and the
+# bound ub(q, h) passes the sub-region by 2 % at 16 bucket bits whatever the
+# seed (0.24 tot(h) against tot(h) / 8 + tot(h) / 128 + 2048 at tot(h) ~ 18000);
+# at 5 x 2^19 a quarter of the segments are two units and ub stays under 0.65
+# of the capacity
+SP_NO_TT_N = 5 << 19
+SP_SMALL_N = 11 * 6144 + 5   # the smallest size class of the bucketed round (tests/test_gpu_first_pass.py)
+SP_TEXTS = ("dna_uniform", "dna_no_tt", "dna_no_tt_small", "binary", "byte256", "alnum", "ascii127")
+SP_XQ_DNA = ("dna_uniform", "dna_no_tt", "dna_no_tt_small")   # per-XCD queues in every mode
+# init_chars of the per-XCD builds: the queues need the fixed-span local sort,
+# whose key span must pass kSubBits bits; the small text's auto K = 13 leaves
+# 9 .. 11, K = 16 gives 15 .. 17 (0: auto)
+SP_XQ_CHARS = {"dna_no_tt_small": 16}
+SP_XQ_OTHER = ("alnum", "byte256")                             # ... at 17 and 18 bucket bits
+SP_BBS = (16, 17, 18)
+SP_ROUNDS_N = 1_500_007
+
+
+def _no_tt(t, seed):
+    """Wherever TT occurs the second T is redrawn from ACG, until no TT is
+    left (the draws: the same splitmix64 stream as the oracle's generator);
+    the text keeps its last symbol T."""
+    t = t.copy()
+    t[-1] = ord("T")
+    if t[-2] == ord("T"):
+        t[-2] = ord("G")
+    acg = np.frombuffer(b"ACG", np.uint8)
+    rng = _Rng(seed)
+    while True:
+        at = np.flatnonzero((t[1:-1] == ord("T")) & (t[:-2] == ord("T"))) + 1
+        if len(at) == 0:
+            break
+        t[at] = acg[rng.below(len(at), 3)]
+    assert not ((t[1:] == ord("T")) & (t[:-1] == ord("T"))).any()
+    return t
+
+
+@functools.lru_cache(maxsize=None)
+def sp_text(name):
+    """The texts of tests/test_gpu_second_pass.py, from the oracle's generator;
+    all end in their largest symbol (the compact layout)."""
+    from oracle import oracle as O
+    if name == "dna_uniform":
+        t = O.gen_text("dna", SP_N, seed=101)
+    elif name == "dna_no_tt":
+        return _no_tt(O.gen_text("dna", SP_NO_TT_N, seed=102), 1102)
+    elif name == "dna_no_tt_small":
+        return _no_tt(O.gen_text("dna", SP_SMALL_N, seed=103), 1103)
+    elif name == "binary":
+        t = O.gen_text("binary", 1 << 20, seed=104)
+    elif name == "byte256":
+        t = O.gen_text("byte256", 1 << 21, seed=105)
+    elif name in ("alnum", "ascii127"):
+        t = O.gen_text(name, 1_500_007, seed=106 + len(name))
+    elif name == "dna_rounds":
+        # later rounds: 300 planted copies of 40-160 symbols keep members
+        # after round 2 (the recipe of test_gpu_parity.py test_key1_round_two)
+        t = O.gen_text("dna", SP_ROUNDS_N, seed=31)
+        rng = _Rng(29)
+        src, dst = rng.below(300, SP_ROUNDS_N - 200), rng.below(300, SP_ROUNDS_N - 200)
+        for a, b, ln in zip(src, dst, 40 + rng.below(300, 120)):
+            t[b:b + ln] = t[a:a + ln].copy()
+    else:
+        raise KeyError(name)
+    t[-1] = t.max()
+    return t
+
+
+@functools.lru_cache(maxsize=None)
+def sp_units(name, bb, unit=UNIT_PK):
+    return second_pass_units(sp_text(name), bb, unit)
+
+
+@functools.lru_cache(maxsize=None)
+def sp_plan(name, bb=None, eonly=False, no_cmp=False, init_chars=0):
+    return text_plan(sp_text(name), init_chars, eonly, bb, no_cmp)
