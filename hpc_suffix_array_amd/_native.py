@@ -111,6 +111,18 @@ LCE_PROBE = 16
 LCE_BLOCK = 64
 LCE_SUPER = 4096
 LCE_HEADER = 4096
+# sa_hamming (include/sa_hip.h SA_HAMMING_*): the largest budget k, the info
+# words ([0] total occurrences, [1] candidates, [2] pieces searched), the
+# positive status of a call stopped by max_candidates, the flags that force one
+# verify path, and the longest pattern a lane verifies in auto mode (csrc/
+# sa_hamming.h kHamLaneBytes)
+HAMMING_MAX_K = 255
+HAMMING_INFO = 3
+HAMMING_TOO_MANY = 1
+HAMMING_LANE = 1
+HAMMING_WAVE = 2
+HAMMING_MODES = {"auto": 0, "lane": HAMMING_LANE, "wave": HAMMING_WAVE}
+HAMMING_LANE_BYTES = 8192
 
 # every symbol include/*.h declares
 DROPIN_SYMBOLS = ["create_suffix_array", "destroy_suffix_array", "build_suffix_array",
@@ -134,6 +146,7 @@ EXT_SYMBOLS = ["sa_context_create", "sa_context_destroy", "sa_context_set_debug"
                "sa_doc_array", "sa_doc_of", "sa_doc_frequency", "sa_doc_list",
                "sa_lce_index_bytes", "sa_lce_build_device", "sa_lcp_min_device", "sa_lce_device",
                "sa_substr_compare_device", "sa_lcp_min", "sa_lce", "sa_substr_compare",
+               "sa_hamming_device", "sa_hamming",
                "sa_dist_begin", "sa_dist_cuts", "sa_dist_plan_cuts", "sa_dist_reserve", "sa_dist_release", "sa_dist_round1", "sa_dist_req_count", "sa_dist_req_fill",
                "sa_dist_answer", "sa_dist_refine",
                "sa_last_error", "sa_host_syncs", "sa_device_count", "sa_version", "sa_struct_size"]
@@ -358,6 +371,12 @@ def lib() -> ctypes.CDLL:
     L.sa_mems.argtypes = [vp, u64, vp, i32, vp, u64, u64, u64, u64, ctypes.c_uint32, vp, vp, vp, u64,
                           ctypes.POINTER(u64)]
     L.sa_mems.restype = i32
+    L.sa_hamming_device.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, u64, u64, ctypes.c_uint32, vp, vp, vp, u64,
+                                    ctypes.POINTER(u64), vp]
+    L.sa_hamming_device.restype = i32
+    L.sa_hamming.argtypes = [vp, u64, vp, i32, vp, vp, u64, u64, u64, ctypes.c_uint32, vp, vp, vp, u64,
+                             ctypes.POINTER(u64)]
+    L.sa_hamming.restype = i32
     L.sa_lpf_device.argtypes = [vp, vp, u64, vp, vp, vp, vp, vp]
     L.sa_lpf_device.restype = i32
     L.sa_lz77_device.argtypes = [vp, u64, vp, vp, vp, vp, vp, u64, ctypes.POINTER(u64), vp]

@@ -405,6 +405,85 @@ def maximal_exact_matches(text, sa, query, min_len: int, max_occ: int = 0, max_c
                       max_occ, max_candidates, mode, return_info)
 
 
+def _hamming_mode(mode: str) -> int:
+    """The SA_HAMMING_* flags of ``mode``."""
+    if mode not in N.HAMMING_MODES:
+        raise ValueError(f"mode {mode!r}: one of {sorted(N.HAMMING_MODES)}")
+    return N.HAMMING_MODES[mode]
+
+
+def _hamming_k(k, max_candidates) -> None:
+    if not 0 <= int(k) <= N.HAMMING_MAX_K:
+        raise ValueError(f"k = {k}: 0 .. {N.HAMMING_MAX_K}")
+    if max_candidates < 0:
+        raise ValueError("max_candidates: 0 (none) or a positive bound")
+
+
+def _hamming_host(t_ptr, n: int, sa_ptr, width: int, patterns, k: int, max_candidates: int, mode: str,
+                  return_info: bool):
+    """sa_hamming over host pointers: a sizing call, then the call that fills
+    the arrays; (offsets int64, positions int64, distances uint8), with the
+    info dict on request."""
+    flags = _hamming_mode(mode)
+    _hamming_k(k, max_candidates)
+    buf, poff = _pack_patterns(patterns)
+    nq = int(poff.size) - 1
+    off = np.zeros(nq + 1, dtype=np.uint64)
+    info = (ctypes.c_uint64 * N.HAMMING_INFO)()
+    L = N.lib()
+
+    def call(pos, dist, cap):
+        rc = N.check(L.sa_hamming(t_ptr if n else None, n, sa_ptr if n else None, width,
+                                  buf.ctypes.data if buf.size else None, poff.ctypes.data, nq, int(k),
+                                  int(max_candidates), flags, off.ctypes.data,
+                                  None if pos is None else pos.ctypes.data,
+                                  None if dist is None else dist.ctypes.data, cap, info), "sa_hamming")
+        if rc == N.HAMMING_TOO_MANY:
+            raise N.SAError(f"sa_hamming: {int(info[1])} candidates are more than max_candidates = "
+                            f"{max_candidates} (raise it, or lower k)")
+
+    call(None, None, 0)
+    total = int(info[0])
+    pos = np.empty(max(total, 1), dtype=np.int64 if width == 8 else np.uint32)
+    dist = np.empty(max(total, 1), dtype=np.uint8)
+    if total:
+        call(pos, dist, total)
+        if int(info[0]) != total:
+            raise N.SAError(f"sa_hamming: {int(info[0])} occurrences after a sizing call that counted {total}")
+    out = (off.astype(np.int64), pos[:total].astype(np.int64), dist[:total].copy())
+    if return_info:
+        return out + ({"total": total, "candidates": int(info[1]), "pieces": int(info[2])},)
+    return out
+
+
+def hamming_search(text, sa, patterns, k: int, max_candidates: int = 0, mode: str = "auto",
+                   return_info: bool = False):
+    """Occurrences of each pattern with at most ``k`` substitutions, searched
+    on the GPU (sa_hamming).
+
+    ``text``, ``sa`` and ``patterns`` are those of find_patterns; ``k`` (0 ..
+    HAMMING_MAX_K) is the budget of every pattern of the call.  Returns
+    ``(offsets, positions, distances)``: pattern q of m bytes occurs at the
+    text positions ``positions[offsets[q]:offsets[q + 1]]`` (int64, ascending,
+    each once), ``p + m <= n``, with ``distances`` (uint8) of them the number
+    of bytes at which ``text[p:p + m]`` and the pattern differ, at most ``k``.
+    The empty pattern occurs at every position of [0, n) with distance 0; a
+    pattern of up to ``k`` bytes occurs at every ``p <= n - m``.  The work is
+    proportional to the candidates, the exact occurrences of the k + 1 pieces
+    of every pattern: ``max_candidates`` (0: none) raises SAError, with the
+    count in the message, instead of enumerating more than that.  ``mode``:
+    "auto", or "lane" / "wave" to force one verify path (tests, A/B runs).
+    ``return_info=True`` appends a dict: ``total``, ``candidates`` and
+    ``pieces`` (nq (k + 1))."""
+    t, s = _text_and_sa(text, sa)
+    _hamming_mode(mode)
+    _hamming_k(k, max_candidates)
+    packed = _pack_patterns(patterns)
+    N.require_device()
+    return _hamming_host(t.ctypes.data, int(t.size), s.ctypes.data, 8 if s.dtype == np.int64 else 4, packed, k,
+                         max_candidates, mode, return_info)
+
+
 def _none_to_minus_one(a: np.ndarray) -> np.ndarray:
     """uint32 / int64 results as int64, "none" (all ones at either width) as -1."""
     out = a.astype(np.int64)
@@ -1059,6 +1138,23 @@ class SuffixArray:
         c = self.p.contents
         return _mems_host(c.str, self.n, ctypes.cast(c.sa, ctypes.c_void_p).value, 4, query, min_len, max_occ,
                           max_candidates, mode, return_info)
+
+    def hamming(self, pattern_or_patterns, k: int, max_candidates: int = 0, mode: str = "auto",
+                return_info: bool = False):
+        """Occurrences with at most ``k`` substitutions, as hamming_search gives
+        them (sa_hamming at width 4 over the object's own str / sa; build()
+        first).  One pattern (bytes, str, bytearray, memoryview or a uint8
+        array) returns ``(positions, distances)``; a sequence of patterns or a
+        ``(buffer, offsets)`` pair returns ``(offsets, positions,
+        distances)``."""
+        N.require_device()
+        c = self.p.contents
+        one = isinstance(pattern_or_patterns, (bytes, bytearray, memoryview, str)) or (
+            isinstance(pattern_or_patterns, np.ndarray) and pattern_or_patterns.dtype == np.uint8
+            and pattern_or_patterns.ndim == 1)
+        out = _hamming_host(c.str, self.n, ctypes.cast(c.sa, ctypes.c_void_p).value, 4,
+                            [pattern_or_patterns] if one else pattern_or_patterns, k, max_candidates, mode, return_info)
+        return out[1:] if one else out
 
     def lpf(self) -> tuple:
         """(lpf, src): the longest previous factor array of the text and its
@@ -1809,6 +1905,30 @@ class DeviceBuilder:
                      "sa_mems_device")
         if rc == N.MEM_TOO_MANY:
             raise N.SAError(f"sa_mems_device: {int(info[1])} candidates are more than max_candidates = "
+                            f"{max_candidates}")
+        return int(info[0]), int(info[1]), int(info[2])
+
+    def hamming(self, d_text, n: int, d_sa, d_pat, pat_bytes: int, d_pat_off, nq: int, k: int, d_off, d_pos, d_dist,
+                out_cap: int, max_candidates: int = 0, mode: str = "auto", stream=None) -> tuple:
+        """Occurrences with at most ``k`` substitutions of the nq patterns at
+        d_pat (pat_bytes bytes, nq + 1 uint64 offsets at d_pat_off), everything
+        in HBM (sa_hamming_device): d_off nq + 1 uint64, d_pos out_cap uint32
+        at any 4-byte alignment, d_dist out_cap bytes or None.  Returns
+        ``(total, candidates, pieces)``.  Positions and distances are written
+        only when the total fits out_cap and d_pos is not None: call once with
+        ``d_pos=None, d_dist=None`` to size the outputs (d_off is filled),
+        allocate, and call again.  Raises SAError when the candidates exceed
+        ``max_candidates``.  Waits for ``stream``."""
+        flags = _hamming_mode(mode)
+        _hamming_k(k, max_candidates)
+        s = _stream(stream)
+        o = self._opt
+        info = (ctypes.c_uint64 * N.HAMMING_INFO)()
+        rc = N.check(self.L.sa_hamming_device(self.ctx, o(d_text), n, o(d_sa), o(d_pat), pat_bytes, o(d_pat_off), nq,
+                                              int(k), int(max_candidates), flags, o(d_off), o(d_pos), o(d_dist),
+                                              int(out_cap), info, s), "sa_hamming_device")
+        if rc == N.HAMMING_TOO_MANY:
+            raise N.SAError(f"sa_hamming_device: {int(info[1])} candidates are more than max_candidates = "
                             f"{max_candidates}")
         return int(info[0]), int(info[1]), int(info[2])
 

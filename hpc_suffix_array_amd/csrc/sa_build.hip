@@ -2533,6 +2533,11 @@ static int scan_i64(int64_t* d_v, uint64_t m, hipStream_t s) {
 // order, all by one query kernel
 #include "sa_lce.h"
 
+// k-mismatch pattern search: the pieces of the patterns by sa_find.h, their
+// hits by sa_locate.h, a verify that also removes the duplicates over
+// sa_mem.h's tiles, the survivors sorted by sa_locate.h
+#include "sa_hamming.h"
+
 extern "C" {
 
 int sa_running_max_i64_device(int64_t* d_v, uint64_t m, void* stream) {

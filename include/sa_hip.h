@@ -746,6 +746,97 @@ int sa_lce(const uint8_t* text, uint64_t n, const void* sa, int sa_width, const 
 int sa_substr_compare(const uint8_t* text, uint64_t n, const void* sa, int sa_width, const uint64_t* i,
                       const uint64_t* li, const uint64_t* j, const uint64_t* lj, uint64_t nq, int8_t* out);
 
+/* ---- k-mismatch pattern search (Hamming distance) --------------------------
+ * (csrc/sa_hamming.h).  Text T of n bytes with its suffix array, a batch of nq
+ * patterns as sa_find takes them (d_pat, pat_bytes, nq + 1 offsets) and one
+ * budget k for the call, 0 <= k <= SA_HAMMING_MAX_K = 255.
+ * An occurrence of pattern P of m bytes is a text position p with p + m <= n
+ * and d(p) <= k, where d(p) = #{ t : P[t] != T[p + t] }.  Bytes as sa_find has
+ * them: binary-safe, 0x00 and 0xFF are ordinary bytes, lengths are explicit.
+ * The empty pattern occurs at every p in [0, n) with distance 0 (sa_find's
+ * [0, n)); m > n or n == 0 gives no occurrence; m <= k is answered as defined:
+ * every p <= n - m is an occurrence (max_candidates is what protects a caller
+ * from it).  Budgets per query are not offered.
+ * The output is CSR over the queries in sa_locate_device's conventions: off
+ * (nq + 1 uint64, off[0] = 0, the total is off[nq]), pos (uint32 text
+ * positions, ascending inside each query, every occurrence exactly once) and
+ * dist (uint8, d(p) of the same slot; may be NULL when only positions are
+ * wanted).
+ * info: SA_HAMMING_INFO uint64 on the host: [0] the total (0 with
+ * SA_HAMMING_TOO_MANY), [1] the candidates, [2] the pieces searched,
+ * nq (k + 1).
+ * max_candidates (0 = none) is the only knob: when the seed occurrences exceed
+ * it nothing is enumerated and the call returns SA_HAMMING_TOO_MANY (a
+ * positive status, as SA_MEM_TOO_MANY) with the info words filled and off all
+ * zero.  There is no cap on the hits of a piece: dropping a frequent piece
+ * would lose occurrences, and this call is complete or says why not.
+ * How it works: piece j = 0 .. k of a pattern is P[b_j, b_{j+1}) with b_j =
+ * floor(j m / (k + 1)); an occurrence with d(p) <= k matches at least one of
+ * the k + 1 pieces exactly (pigeonhole), so p + b_j is among that piece's
+ * exact occurrences.  The pieces of the batch are searched by sa_find_device
+ * (an empty piece, m < k + 1, gets [0, n)) and their hits listed by
+ * sa_locate_device.  A candidate (pattern, piece j, hit h) with p = h - b_j is
+ * kept exactly when it is valid (h >= b_j, p + m <= n), d(p) <= k, and j is
+ * the first piece of the pattern that matches T exactly at p: each occurrence
+ * passes once, without a sort, a hash or an atomic.  The survivors are
+ * compacted and sorted per query by sa_locate_device's sort, whose limit on a
+ * sorted total is inherited: more than 2^32 - 1 occurrences in all are
+ * SA_E_INVALID.  The distances are computed again for the survivors in output
+ * order.  A lane verifies by 8-byte words; the candidates of patterns longer
+ * than 8192 bytes go to a wavefront (512 bytes a step).  Temporaries are about
+ * 4.2 bytes per candidate on top of sa_locate_device's own, 4 bytes per
+ * occurrence and 24 bytes per piece.  DESIGN.md section 21. */
+#define SA_HAMMING_MAX_K 255
+#define SA_HAMMING_INFO 3
+#define SA_HAMMING_TOO_MANY 1
+#define SA_HAMMING_LANE 1u   /* tests, A/B: every candidate verified by its own lane */
+#define SA_HAMMING_WAVE 2u   /* tests, A/B: every candidate verified by a wavefront */
+
+/* d_text: n bytes, d_sa: n uint32, d_pat: pat_bytes bytes, d_pat_off: nq + 1
+ * uint64 (clamped to pat_bytes, a decreasing pair is the empty pattern, as
+ * sa_find_device reads them), d_off: nq + 1 uint64, d_pos: out_cap uint32 or
+ * NULL, d_dist: out_cap bytes or NULL, all in device memory.  When d_pos is
+ * NULL, or when the total exceeds out_cap, d_off and info are filled, nothing
+ * in d_pos / d_dist is touched and the call returns SA_OK: the sizing call,
+ * after which the caller allocates and calls again.  Exactly [0, total) of
+ * d_pos and d_dist and d_off[0, nq] are written; d_pos may have any 4-byte
+ * alignment, d_dist any (d_off 8-byte).
+ * Synchronises `stream`.  Host waits per call: one for the candidate count,
+ * sa_locate_device's own over the pieces (one; two when a piece has more than
+ * SA_LOCATE_TILE hits), one for the total, sa_locate_device's own over the
+ * survivors (one; more when a query has more than SA_LOCATE_TILE
+ * occurrences), and one at the end when d_dist is given.  Temporaries are
+ * stream-ordered allocations (SA_E_NOMEM when one fails).
+ * nq == 0: SA_OK, off[0] = 0, no kernel.  n == 0: SA_OK, off all zero, no
+ * kernel.
+ * Checked before any HIP call (SA_E_INVALID, each with its own message): a
+ * NULL ctx, info or d_off; a NULL d_text or d_sa with n > 0; a NULL d_pat with
+ * pat_bytes > 0; a NULL d_pat_off with nq > 0; n, nq or nq (k + 1) above
+ * 2^32 - 1; k above SA_HAMMING_MAX_K; unknown flags (or both of them); d_dist
+ * without d_pos; an output that is one of the inputs or another output.
+ * Precondition: d_sa is a valid suffix array of the text.  Without it
+ * occurrences may be missing, but what is listed is an occurrence with its
+ * distance, and no load leaves d_text[0, n), d_sa[0, n), d_pat[0, pat_bytes),
+ * the offsets or the temporaries: a hit >= n reads as invalid, the piece
+ * offsets are clamped as sa_find_device clamps them, and every compare ends at
+ * min(m, n - p). */
+int sa_hamming_device(sa_context* ctx, const uint8_t* d_text, uint64_t n, const uint32_t* d_sa, const uint8_t* d_pat,
+                      uint64_t pat_bytes, const uint64_t* d_pat_off /* nq + 1 */, uint64_t nq, uint64_t k,
+                      uint64_t max_candidates, uint32_t flags, uint64_t* d_off /* nq + 1 */, uint32_t* d_pos,
+                      uint8_t* d_dist, uint64_t out_cap, uint64_t info[SA_HAMMING_INFO], void* stream);
+/* Host in, host out over the staging of the other host forms: sa and pos_out
+ * have width sa_width (4 or 8; a width-8 SA entry outside [0, n) is
+ * SA_E_INVALID before any device work), dist_out is uint8, pat_off must not
+ * decrease and pat holds pat_off[nq] bytes.  The total is found first and the
+ * device outputs are allocated then, so a caller may pass out_cap = 0 and NULL
+ * outputs to learn the total (info[0]) and off_out, and call again.  nq == 0
+ * and n == 0 need no device.  Arguments are checked as the device form checks
+ * them. */
+int sa_hamming(const uint8_t* text, uint64_t n, const void* sa, int sa_width, const uint8_t* pat,
+               const uint64_t* pat_off /* nq + 1 */, uint64_t nq, uint64_t k, uint64_t max_candidates, uint32_t flags,
+               uint64_t* off_out /* nq + 1 */, void* pos_out /* width sa_width */, uint8_t* dist_out, uint64_t out_cap,
+               uint64_t info[SA_HAMMING_INFO]);
+
 /* ---- maximal exact matches of a query against the text -------------------
  * (csrc/sa_mem.h).  Text T of n bytes with its suffix array, query Q of m
  * bytes, min_len = L >= 1.  A MEM is a triple (i, p, l) with all of:
