@@ -175,8 +175,7 @@ struct sa_context {
     uint32_t* words = nullptr;     // [0..2] = D, m, G; [3] = check error flags
     uint32_t* alpha = nullptr;     // 256 byte counts
     uint16_t* code = nullptr;      // 256 byte -> dense code 1..sigma
-    uint32_t* host_words = nullptr;  // pinned (4096 words): 64 words, 256 counts, 128 words of codes at 320, the text tail (64 B) at 2048,
-                                     // per-rank counts of the range-partitioned build at 1024
+    uint32_t* host_words = nullptr;  // pinned, sa::kHostWords words: the regions are sa_limits.h's table (kHw*)
     hipEvent_t ev[sa::kEvPool + sa::kRoundEv + 1];   // Timer pairs, the round boundaries, a read-back (kSyncEv)
     int ev_ready = 0;
     sa::DistState* dist = nullptr;   // range-partitioned build state (sa_dist.h)
@@ -194,6 +193,13 @@ struct sa_context {
 };
 
 namespace sa {
+
+// region R of the pinned words as the N 64-bit words its reader reads: the table holds exactly those
+template <HwId R, int N> static uint64_t* host_u64(sa_context* c) {
+    static_assert(hw(R).wide && hw(R).len == 2 * N, "sa_limits.h: a region is as long as what is read from it");
+    return reinterpret_cast<uint64_t*>(c->host_words + hw(R).at);
+}
+static_assert(kLongRounds + 1 <= (int)hw(kHwLcpCounts).len && kMaxK <= (int)hw(kHwTail).len * 4, "sa_limits.h's regions");
 
 // keys[0] / vals_alt elements for the padded first-pass segments of the
 // bucketed round (sa_round1.h kPadMinN..kPadMaxN; their bound sums to < 1.1 n)
@@ -911,8 +917,8 @@ static int build_reference(sa_context* c, const uint8_t* d_text, uint64_t n, uin
     // first ranks: dense codes 1..sigma of the bytes present (the order of
     // manber_myers.c:90's text[i] + 1, so D_j and the round count are the
     // reference's; the first key spans 2 bit_width(sigma) bits, not 18)
-    uint32_t* h_alpha = c->host_words + 64;
-    uint16_t* h_code = reinterpret_cast<uint16_t*>(c->host_words + 320);
+    uint32_t* h_alpha = c->host_words + hw(kHwAlpha).at;
+    uint16_t* h_code = reinterpret_cast<uint16_t*>(c->host_words + hw(kHwCode).at);
     SA_HIP(hipMemsetAsync(c->alpha, 0, 8 * 4, s));
     tm.begin(SA_K_ALPHABET);
     {
@@ -1247,9 +1253,10 @@ static int pivot_round(sa_context* c, int ui, int uo, uint64_t n, uint64_t m, ui
         SA_HIP(hipGetLastError());
         add_bytes(st, SA_K_PIVOT_COUNT, 8 * m);
     }
-    SA_HIP(hipMemcpyAsync(c->host_words + 16, c->totals, 12, hipMemcpyDeviceToHost, s));
+    SA_HIP(hipMemcpyAsync(c->host_words + hw(kHwTotals).at, c->totals, 12, hipMemcpyDeviceToHost, s));
     SA_HIP(host_sync(s));
-    const uint64_t t0 = c->host_words[16], t1 = c->host_words[17], t2 = c->host_words[18];
+    const uint32_t* ht = c->host_words + hw(kHwTotals).at;
+    const uint64_t t0 = ht[0], t1 = ht[1], t2 = ht[2];
     if (t0 + t1 + t2 != m) return set_err(SA_E_INTERNAL, "pivot classes %llu + %llu + %llu != %llu",
                                           (unsigned long long)t0, (unsigned long long)t1, (unsigned long long)t2,
                                           (unsigned long long)m);
@@ -1283,11 +1290,11 @@ static int pivot_round(sa_context* c, int ui, int uo, uint64_t n, uint64_t m, ui
     SA_HIP(hipGetLastError());
     add_bytes(st, SA_K_PIVOT_WRITE, tied ? 12 * m + 16 * t1 + 12 * mr : 12 * m + 12 * m);
     if (tied) {
-        SA_HIP(hipMemcpyAsync(c->host_words + 20, c->totals + 4, 12, hipMemcpyDeviceToHost, s));
+        SA_HIP(hipMemcpyAsync(c->host_words + hw(kHwUTotals).at, c->totals + 4, 12, hipMemcpyDeviceToHost, s));
         SA_HIP(host_sync(s));
-        T = c->host_words[20];
-        Gt = c->host_words[21];
-        Dt = c->host_words[22];
+        T = c->host_words[hw(kHwUTotals).at];
+        Gt = c->host_words[hw(kHwUTotals).at + 1];
+        Dt = c->host_words[hw(kHwUTotals).at + 2];
         if (T > t1 || Gt > G || Dt > G)
             return set_err(SA_E_INTERNAL, "tied blocks %llu / %llu / %llu out of range", (unsigned long long)T,
                            (unsigned long long)Gt, (unsigned long long)Dt);
@@ -1357,9 +1364,10 @@ static int pivot_round1(sa_context* c, uint64_t n, uint32_t bits1, uint32_t* d_s
     uint32_t* const tid = gs + 4;
     uint32_t* const gP = c->vals_alt;   // 3 x 2
     uint32_t* const cc = c->hist;       // 3 x chunks class counts
-    c->host_words[24] = 0;
-    c->host_words[25] = (uint32_t)n;
-    SA_HIP(hipMemcpyAsync(gs, c->host_words + 24, 8, hipMemcpyHostToDevice, s));
+    uint32_t* hg = c->host_words + hw(kHwGsInit).at;
+    hg[0] = 0;
+    hg[1] = (uint32_t)n;
+    SA_HIP(hipMemcpyAsync(gs, hg, 8, hipMemcpyHostToDevice, s));
     tm.begin(SA_K_PIVOT_COUNT);
     hipLaunchKernelGGL((k_pivot_pass<0, true>), dim3(ch.chunks), dim3(kBlock), 0, s, keys, nullptr, nullptr, ch,
                        (const uint32_t*)gs, nullptr, 1u, 0u, cc, gP, nullptr, nullptr, nullptr, nullptr, TiedOut{});
@@ -1367,9 +1375,10 @@ static int pivot_round1(sa_context* c, uint64_t n, uint32_t bits1, uint32_t* d_s
     tm.end();
     SA_HIP(hipGetLastError());
     add_bytes(st, SA_K_PIVOT_COUNT, 8 * n);
-    SA_HIP(hipMemcpyAsync(c->host_words + 16, c->totals, 12, hipMemcpyDeviceToHost, s));
+    SA_HIP(hipMemcpyAsync(c->host_words + hw(kHwTotals).at, c->totals, 12, hipMemcpyDeviceToHost, s));
     SA_HIP(host_sync(s));
-    const uint64_t t0 = c->host_words[16], t1 = c->host_words[17], t2 = c->host_words[18];
+    const uint32_t* ht = c->host_words + hw(kHwTotals).at;
+    const uint64_t t0 = ht[0], t1 = ht[1], t2 = ht[2];
     if (t0 + t1 + t2 != n) return set_err(SA_E_INTERNAL, "round-1 pivot classes %llu + %llu + %llu != %llu",
                                           (unsigned long long)t0, (unsigned long long)t1, (unsigned long long)t2,
                                           (unsigned long long)n);
@@ -1394,9 +1403,10 @@ static int pivot_round1(sa_context* c, uint64_t n, uint32_t bits1, uint32_t* d_s
     tm.end();
     SA_HIP(hipGetLastError());
     add_bytes(st, SA_K_PIVOT_WRITE, 8 * n + 16 * t1 + 12 * mr);
-    SA_HIP(hipMemcpyAsync(c->host_words + 20, c->totals + 4, 12, hipMemcpyDeviceToHost, s));
+    SA_HIP(hipMemcpyAsync(c->host_words + hw(kHwUTotals).at, c->totals + 4, 12, hipMemcpyDeviceToHost, s));
     SA_HIP(host_sync(s));
-    const uint64_t T = c->host_words[20], Gt = c->host_words[21], Dt = c->host_words[22];
+    const uint32_t* hu = c->host_words + hw(kHwUTotals).at;
+    const uint64_t T = hu[0], Gt = hu[1], Dt = hu[2];
     if (T > t1 || Gt > 1 || Dt > 1)
         return set_err(SA_E_INTERNAL, "round-1 tied block %llu / %llu / %llu out of range", (unsigned long long)T,
                        (unsigned long long)Gt, (unsigned long long)Dt);
@@ -1428,11 +1438,11 @@ static int build_packed(sa_context* c, const uint8_t* d_text, uint64_t n, uint32
     rc = ensure_u_capacity(c, n);
     if (rc) return rc;
     tm.round_mark();
-    uint32_t* h_alpha = c->host_words + 64;
-    uint16_t* h_code = reinterpret_cast<uint16_t*>(c->host_words + 320);
+    uint32_t* h_alpha = c->host_words + hw(kHwAlpha).at;
+    uint16_t* h_code = reinterpret_cast<uint16_t*>(c->host_words + hw(kHwCode).at);
     // the text's last bytes: the compact key layout's check (short_suffix_ties)
     const uint32_t tail_n = (uint32_t)std::min<uint64_t>(n, (uint64_t)kMaxK);
-    uint8_t* h_tail = reinterpret_cast<uint8_t*>(c->host_words + 2048);
+    uint8_t* h_tail = reinterpret_cast<uint8_t*>(c->host_words + hw(kHwTail).at);
     uint32_t sigma = 0, K = 0, Kb = 0;
     BucketPlan bp;
     const int r1 = opts ? opts->round1 : SA_ROUND1_AUTO;
@@ -1952,7 +1962,7 @@ static int check_device(sa_context* c, const uint8_t* d_text, uint64_t n, const 
     int rc = ensure_capacity(c, n);
     if (rc) return rc;
     uint32_t* isa = c->rank;
-    uint32_t* err = c->words + 3;
+    uint32_t* err = c->words + kChkErrWord;
     uint32_t* cur1 = c->hist;
     uint32_t* cur2 = c->hist + kCur2;
     uint64_t* ends = reinterpret_cast<uint64_t*>(c->vals_alt);
@@ -1993,13 +2003,13 @@ static int check_device(sa_context* c, const uint8_t* d_text, uint64_t n, const 
             }
         }
         SA_HIP(hipGetLastError());
-        SA_HIP(hipMemcpyAsync(c->host_words + 3, err, 4, hipMemcpyDeviceToHost, s));
+        SA_HIP(hipMemcpyAsync(c->host_words + kChkErrWord, err, 4, hipMemcpyDeviceToHost, s));
         SA_HIP(host_sync(s));
         SA_TRACE("check (%u stripes asked, %u / %u run in pass A / B): error bits %#x", stripes, ran[0], ran[1],
-                 c->host_words[3]);
-        if (!(c->host_words[3] & 128u)) break;   // else a stripe overflowed: again with one
+                 c->host_words[kChkErrWord]);
+        if (!(c->host_words[kChkErrWord] & 128u)) break;   // else a stripe overflowed: again with one
     }
-    return c->host_words[3] == 0 ? 1 : 0;
+    return c->host_words[kChkErrWord] == 0 ? 1 : 0;
 }
 
 // ---------------------------------------------------------------------------
@@ -2031,18 +2041,18 @@ static int lcp_device(sa_context* c, const uint8_t* d_text, uint64_t n, const ui
     // PHI' = PHI + 1 (0: none) by the coalesced permutation (its hole flag for
     // the smallest suffix, which has no predecessor, is expected: words[12])
     for (uint32_t stripes : {kChkStripes, 1u}) {
-        SA_HIP(hipMemsetAsync(c->words + 12, 0, 4, s));
-        SA_TRY(place_by_permutation<PhiSrc, 2>(c, PhiSrc{d_sa}, n, phi, c->words + 12, s, stripes));
+        SA_HIP(hipMemsetAsync(c->words + kPlaceErrWord, 0, 4, s));
+        SA_TRY(place_by_permutation<PhiSrc, 2>(c, PhiSrc{d_sa}, n, phi, c->words + kPlaceErrWord, s, stripes));
         if (stripes == 1) {
             SA_TRACE("lcp PHI (%u stripes asked, %u run)", stripes, perm_stripes_run(c, n, stripes));
             break;
         }
         // a level-1 stripe that overflowed (only an adversarial SA) lost pairs
-        SA_HIP(hipMemcpyAsync(c->host_words + 12, c->words + 12, 4, hipMemcpyDeviceToHost, s));
+        SA_HIP(hipMemcpyAsync(c->host_words + kPlaceErrWord, c->words + kPlaceErrWord, 4, hipMemcpyDeviceToHost, s));
         SA_HIP(host_sync(s));
         SA_TRACE("lcp PHI (%u stripes asked, %u run): error bits %#x", stripes, perm_stripes_run(c, n, stripes),
-                 c->host_words[12]);
-        if (!(c->host_words[12] & 128u)) break;
+                 c->host_words[kPlaceErrWord]);
+        if (!(c->host_words[kPlaceErrWord] & 128u)) break;
     }
     hipLaunchKernelGGL(k_plcp_irreducible, dim3(grid), dim3(kBlock), 0, s, d_text, n, (const uint32_t*)phi, v,
                        c->keys[0], c->vals_alt, cnt);
@@ -2069,39 +2079,39 @@ static int lcp_device(sa_context* c, const uint8_t* d_text, uint64_t n, const ui
         uint32_t* isa1 = c->vals_alt;
         for (int pass = 0; pass < 2; ++pass) {
             for (uint32_t stripes : {kChkStripes, 1u}) {
-                SA_HIP(hipMemsetAsync(c->words + 12, 0, 4, s));
+                SA_HIP(hipMemsetAsync(c->words + kPlaceErrWord, 0, 4, s));
                 if (pass == 0)
-                    SA_TRY(place_by_permutation<IsaSrc, 3>(c, IsaSrc{{d_sa}}, n, isa1, c->words + 12, s, stripes));
+                    SA_TRY(place_by_permutation<IsaSrc, 3>(c, IsaSrc{{d_sa}}, n, isa1, c->words + kPlaceErrWord, s, stripes));
                 else
-                    SA_TRY(place_by_permutation<PlcpSrc, 4>(c, PlcpSrc{isa1, v}, n, d_lcp, c->words + 12, s,
+                    SA_TRY(place_by_permutation<PlcpSrc, 4>(c, PlcpSrc{isa1, v}, n, d_lcp, c->words + kPlaceErrWord, s,
                                                             stripes));
                 if (stripes == 1) {
                     SA_TRACE("lcp %s (%u stripes asked, %u run)", pass ? "PLCP" : "ISA", stripes,
                              perm_stripes_run(c, n, stripes));
                     break;
                 }
-                SA_HIP(hipMemcpyAsync(c->host_words + 12, c->words + 12, 4, hipMemcpyDeviceToHost, s));
+                SA_HIP(hipMemcpyAsync(c->host_words + kPlaceErrWord, c->words + kPlaceErrWord, 4, hipMemcpyDeviceToHost, s));
                 SA_HIP(host_sync(s));
                 SA_TRACE("lcp %s (%u stripes asked, %u run): error bits %#x", pass ? "PLCP" : "ISA", stripes,
-                         perm_stripes_run(c, n, stripes), c->host_words[12]);
-                if (!(c->host_words[12] & 128u)) break;
+                         perm_stripes_run(c, n, stripes), c->host_words[kPlaceErrWord]);
+                if (!(c->host_words[kPlaceErrWord] & 128u)) break;
             }
         }
         hipLaunchKernelGGL(k_lcp_best, dim3(grid), dim3(kBlock), 0, s, (const uint32_t*)d_lcp, n, best);
     }
     SA_HIP(hipGetLastError());
-    SA_HIP(hipMemcpyAsync(c->host_words + 8, best, 8, hipMemcpyDeviceToHost, s));
-    SA_HIP(hipMemcpyAsync(c->host_words + 16, cnt, (kLongRounds + 1) * 4, hipMemcpyDeviceToHost, s));
+    SA_HIP(hipMemcpyAsync(c->host_words + hw(kHwLcpBest).at, best, 8, hipMemcpyDeviceToHost, s));
+    SA_HIP(hipMemcpyAsync(c->host_words + hw(kHwLcpCounts).at, cnt, (kLongRounds + 1) * 4, hipMemcpyDeviceToHost, s));
     SA_HIP(host_sync(s));
     // every pair resolves by the last window (it reaches n); a pair left over is a bug
     uint64_t lo_end = kDirect;
     int rounds = 0;
     while (rounds < kLongRounds && lo_end < n) { lo_end *= 4; ++rounds; }
-    if (c->host_words[16 + rounds] != 0)
-        return set_err(SA_E_INTERNAL, "%u LCP pairs unresolved", c->host_words[16 + rounds]);
-    SA_TRACE("lcp: direct-overflow pairs %u, rounds %d", c->host_words[16], rounds);
+    const uint32_t* hl = c->host_words + hw(kHwLcpCounts).at;
+    if (hl[rounds] != 0) return set_err(SA_E_INTERNAL, "%u LCP pairs unresolved", hl[rounds]);
+    SA_TRACE("lcp: direct-overflow pairs %u, rounds %d", hl[0], rounds);
     unsigned long long b;
-    std::memcpy(&b, c->host_words + 8, 8);
+    std::memcpy(&b, c->host_words + hw(kHwLcpBest).at, 8);
     const uint64_t len = b >> 32;
     if (len) {
         const uint64_t r = 0xFFFFFFFFull - (b & 0xFFFFFFFFull);
@@ -2187,7 +2197,7 @@ int sa_context_create(int device, uint64_t max_n, sa_context** out) {
         hipMalloc(&c->lsd, (2 * kMaxPasses * kLsdMaxRadix + kMaxPasses) * 4 + 64) != hipSuccess ||
         hipMalloc(&c->lsdx, kLsdXqWords * 4) != hipSuccess ||
         hipMalloc(&c->segw, (kBstartOff + 2 * kBstartWords) * 4) != hipSuccess ||
-        hipHostMalloc(&c->host_words, 16384, hipHostMallocDefault) != hipSuccess) {
+        hipHostMalloc(&c->host_words, kHostWords * 4, hipHostMallocDefault) != hipSuccess) {
         (void)hipGetLastError();
         sa_context_destroy(c);
         return set_err(SA_E_NOMEM, "context allocation failed");
@@ -2498,6 +2508,9 @@ static int scan_i64(int64_t* d_v, uint64_t m, hipStream_t s) {
 // are summed by scan_i64 above)
 #include "sa_locate.h"
 
+// what the queries below share: candidate tiles and lists, lists materialised then sorted
+#include "sa_query.h"
+
 // maximal exact matches of a query: seeds by sa_match.h, their hits by
 // sa_locate.h, the left check, the right extension and the compaction here
 #include "sa_mem.h"
@@ -2518,13 +2531,13 @@ static int scan_i64(int64_t* d_v, uint64_t m, hipStream_t s) {
 
 // an FM-index over (bwt, primary): rank blocks counted from the LF kernels'
 // histogram, backward-search counting, locating through a sampled SA whose
-// hit lists sa_locate.h sorts
+// hit lists sa_query.h's ListSort sorts
 #include "sa_fm.h"
 
 // document collections over one suffix array: the document array and the
 // previous-occurrence array (the context's radix sort), document frequency
 // of SA intervals in one filtered pass, document listing whose ids
-// sa_locate.h sorts
+// sa_query.h's ListSort sorts
 #include "sa_docs.h"
 
 // longest common extensions: a range-minimum index over the LCP array (block
@@ -2535,7 +2548,7 @@ static int scan_i64(int64_t* d_v, uint64_t m, hipStream_t s) {
 
 // k-mismatch pattern search: the pieces of the patterns by sa_find.h, their
 // hits by sa_locate.h, a verify that also removes the duplicates over
-// sa_mem.h's tiles, the survivors sorted by sa_locate.h
+// sa_query.h's tiles, the survivors sorted by its sort_lists
 #include "sa_hamming.h"
 
 extern "C" {
@@ -2618,7 +2631,7 @@ int sa_pack_keys_device(sa_context* ctx, const uint8_t* d_text, uint64_t n, uint
     SA_HIP(hipSetDevice(ctx->device));
     // the caller's code[] may be a temporary: stage it in the context's pinned
     // words and wait for the copy before returning
-    uint16_t* h_code = reinterpret_cast<uint16_t*>(ctx->host_words + 320);
+    uint16_t* h_code = reinterpret_cast<uint16_t*>(ctx->host_words + hw(kHwCode).at);
     std::memcpy(h_code, code, 512);
     SA_HIP(hipMemcpyAsync(ctx->code, h_code, 512, hipMemcpyHostToDevice, s));
     SA_HIP(host_sync(s));

@@ -50,6 +50,7 @@
 
 
 constexpr int kDistMaxWorld = 1024;
+static_assert(kDistMaxWorld <= (int)hw(kHwDistCounts).len, "the pinned per-rank counts");
 
 struct DistState {
     uint64_t n = 0;
@@ -350,14 +351,14 @@ static int dist_begin(sa_context* c, const uint8_t* d_text, uint64_t n, int worl
     d->planned = false;
     d->text = d_text;
     d->rounds = 0;
-    uint16_t* h_code = reinterpret_cast<uint16_t*>(c->host_words + 320);
+    uint16_t* h_code = reinterpret_cast<uint16_t*>(c->host_words + hw(kHwCode).at);
     uint32_t sigma = 0;
     for (int b = 0; b < 256; ++b) h_code[b] = ((present[b >> 5] >> (b & 31)) & 1u) ? (uint16_t)(++sigma) : 0;
     c->dna = sigma == 4 && h_code['A'] && h_code['C'] && h_code['G'] && h_code['T'];
     SA_HIP(hipMemcpyAsync(c->code, h_code, 256 * 2, hipMemcpyHostToDevice, s));
     // the text's tail (every rank holds the text: all take the same layout)
     const uint32_t tail_n = (uint32_t)std::min<uint64_t>(n, (uint64_t)kMaxK);
-    uint8_t* h_tail = reinterpret_cast<uint8_t*>(c->host_words + 2048);
+    uint8_t* h_tail = reinterpret_cast<uint8_t*>(c->host_words + hw(kHwTail).at);
     SA_HIP(hipMemcpyAsync(h_tail, d_text + (n - tail_n), tail_n, hipMemcpyDeviceToHost, s));
     SA_HIP(host_sync(s));
     d->sigma = sigma;
@@ -570,7 +571,7 @@ static int dist_req_count(sa_context* c, uint64_t h, uint64_t* h_counts, hipStre
                            d->text, d->n, (const uint16_t*)c->code, d->bp.bs, (const uint16_t*)d->owner_tab,
                            dist_cshift(*d), d->owner, d->cnt);
         SA_HIP(hipGetLastError());
-        uint32_t* hc = c->host_words + 1024;   // pinned scratch (W <= kDistMaxWorld)
+        uint32_t* hc = c->host_words + hw(kHwDistCounts).at;   // pinned scratch (W <= kDistMaxWorld)
         SA_HIP(hipMemcpyAsync(hc, d->cnt, W * 4, hipMemcpyDeviceToHost, s));
         SA_HIP(host_sync(s));
         for (int q = 0; q < W; ++q) {
@@ -628,7 +629,7 @@ static int dist_refine(sa_context* c, uint64_t h, const uint64_t* d_ans, uint32_
     if (!d) return set_err(SA_E_INVALID, "no distributed state");
     info->heads = 0;
     // a request outside this rank's range (k_dist_answer) is a bug
-    uint32_t* hc = c->host_words + 1024;
+    uint32_t* hc = c->host_words + hw(kHwDistCounts).at;
     SA_HIP(hipMemcpyAsync(hc, d->cnt + 2 * kDistMaxWorld, 4, hipMemcpyDeviceToHost, s));
     SA_HIP(host_sync(s));
     if (hc[0]) return set_err(SA_E_INTERNAL, "rank request outside this rank's bucket range");

@@ -39,7 +39,7 @@
 // the class and chunks of a query, the key width of D) compiles on the host:
 // tests/cpp/docs_check.cpp checks it against brute force.
 // Measurements: DESIGN.md section 19.
-// The HIP part needs sa_host.h, sa_locate.h and sa_fm.h (k_fm_ranges) before it.
+// The HIP part needs sa_host.h, sa_locate.h and sa_query.h (ListSort) before it.
 #pragma once
 #include <stdint.h>
 
@@ -109,7 +109,6 @@ static_assert(kDocNone == SA_DOC_NONE && kDocTile == SA_DOC_TILE && kDocGroupMax
               "the header's constants");
 static_assert(kDocTile == 8 * kBlock && kWave % kDocGroup == 0, "8 ranks per lane and chunk");
 constexpr uint32_t kDocGrid = 1024;       // workgroups of the grids of the forms that take no context
-constexpr int kDocHostWord = 3520;        // host_words: total, long queries (8 bytes each)
 
 struct DocOffLds {
     const uint32_t* p;
@@ -349,9 +348,7 @@ static int doc_array_device(sa_context* c, uint64_t n, const uint32_t* d_sa, con
     SA_TRY(doc_check_out(d_da, "d_da"));
     SA_TRY(doc_check_out(d_prev, "d_prev"));
     if (d_da && d_da == d_prev) return set_err(SA_E_INVALID, "d_da may not alias d_prev");
-    if ((d_da && ((const void*)d_da == (const void*)d_sa || (const void*)d_da == (const void*)d_doc_off)) ||
-        (d_prev && ((const void*)d_prev == (const void*)d_sa || (const void*)d_prev == (const void*)d_doc_off)))
-        return set_err(SA_E_INVALID, "an output may not alias d_sa or d_doc_off");
+    SA_TRY(check_no_alias({d_da, d_prev}, {d_sa, d_doc_off}, "an output may not alias d_sa or d_doc_off"));
     if (n == 0) return SA_OK;
     SA_HIP(hipSetDevice(c->device));
     const uint32_t grid = doc_grid(n, (uint64_t)kBlock * 16, (uint64_t)c->cus * 8);
@@ -386,9 +383,7 @@ static int doc_of_device(const uint64_t* d_doc_off, uint64_t D, uint64_t n, cons
     SA_TRY(doc_check_out(d_doc, "d_doc"));
     SA_TRY(doc_check_out(d_rel, "d_rel"));
     if (d_doc && d_doc == d_rel) return set_err(SA_E_INVALID, "d_doc may not alias d_rel");
-    if ((d_doc && ((const void*)d_doc == (const void*)d_pos || (const void*)d_doc == (const void*)d_doc_off)) ||
-        (d_rel && ((const void*)d_rel == (const void*)d_pos || (const void*)d_rel == (const void*)d_doc_off)))
-        return set_err(SA_E_INVALID, "an output may not alias d_pos or d_doc_off");
+    SA_TRY(check_no_alias({d_doc, d_rel}, {d_pos, d_doc_off}, "an output may not alias d_pos or d_doc_off"));
     if (count == 0) return SA_OK;
     doc_map_launch<true>(doc_grid(count, (uint64_t)kBlock * 16, kDocGrid), s, d_pos, count, n, d_doc_off, D, d_doc, d_rel,
                          nullptr, nullptr);
@@ -408,9 +403,7 @@ static int doc_frequency_device(uint64_t n, const uint32_t* d_prev, const uint32
     if (!d_hi) return set_err(SA_E_INVALID, "d_hi is NULL");
     if (!d_df) return set_err(SA_E_INVALID, "d_df is NULL");
     SA_TRY(doc_check_out(d_df, "d_df"));
-    if ((const void*)d_df == (const void*)d_prev || (const void*)d_df == (const void*)d_lo ||
-        (const void*)d_df == (const void*)d_hi)
-        return set_err(SA_E_INVALID, "d_df may not alias an input");
+    SA_TRY(check_no_alias({d_df}, {d_prev, d_lo, d_hi}, "d_df may not alias an input"));
     LocBuf ch;
     SA_TRY(ch.alloc((nq + 1) * 8, s));
     hipLaunchKernelGGL(k_doc_freq_group, dim3(doc_grid(nq, kBlock / kDocGroup, 4 * kDocGrid)), dim3(kBlock), 0, s, d_prev,
@@ -431,7 +424,7 @@ static int doc_list_check(const sa_context* c, uint64_t n, const uint32_t* d_da,
     if (!total) return set_err(SA_E_INVALID, "total is NULL");
     if (n > 0xFFFFFFFFull) return set_err(SA_E_INVALID, "n too large");
     if (nq > 0xFFFFFFFFull) return set_err(SA_E_INVALID, "nq too large");
-    if (flags & ~(uint32_t)SA_DOC_RANK_ORDER) return set_err(SA_E_INVALID, "unknown flags %#x", flags);
+    SA_TRY(check_flags(flags, SA_DOC_RANK_ORDER));
     if (!d_off) return set_err(SA_E_INVALID, "d_off is NULL");
     if ((uintptr_t)d_off & 7u) return set_err(SA_E_INVALID, "d_off is not 8-byte aligned");
     SA_TRY(doc_check_out(d_docs, "d_docs"));
@@ -441,10 +434,7 @@ static int doc_list_check(const sa_context* c, uint64_t n, const uint32_t* d_da,
         if (!d_lo) return set_err(SA_E_INVALID, "d_lo is NULL");
         if (!d_hi) return set_err(SA_E_INVALID, "d_hi is NULL");
     }
-    const void* in[4] = {d_da, d_prev, d_lo, d_hi};
-    for (const void* p : in)
-        if (p && (p == (const void*)d_off || p == (const void*)d_docs))
-            return set_err(SA_E_INVALID, "an output may not alias an input");
+    SA_TRY(check_no_alias({d_off, d_docs}, {d_da, d_prev, d_lo, d_hi}, "an output may not alias an input"));
     if (d_docs && (const void*)d_docs == (const void*)d_off) return set_err(SA_E_INVALID, "d_docs may not alias d_off");
     return SA_OK;
 }
@@ -460,12 +450,8 @@ static int doc_list_device(sa_context* c, uint64_t n, const uint32_t* d_da, cons
     SA_TRY(doc_list_check(c, n, d_da, d_prev, d_lo, d_hi, nq, flags, d_off, d_docs, total));
     *total = 0;
     SA_HIP(hipSetDevice(c->device));
-    if (nq == 0) {
-        SA_HIP(hipMemsetAsync(d_off, 0, 8, s));
-        SA_HIP(host_sync(s));
-        return SA_OK;
-    }
-    uint64_t* h = reinterpret_cast<uint64_t*>(c->host_words + kDocHostWord);
+    if (nq == 0) return empty_csr(d_off, 0, s);
+    uint64_t* h = host_u64<kHwDocs, 2>(c);
     {
         LocBuf w;   // the long queries (16 bytes) | df
         SA_TRY(w.alloc(16 + nq * 4, s));
@@ -488,16 +474,9 @@ static int doc_list_device(sa_context* c, uint64_t n, const uint32_t* d_da, cons
     const bool direct = (flags & SA_DOC_RANK_ORDER) != 0;
     if (!direct && sum > 0xFFFFFFFFull)
         return set_err(SA_E_INVALID, "%llu ids are more than 2^32 - 1: cap them with max_docs", (unsigned long long)sum);
-    LocBuf tmp;   // the ids (4 x total) | lo2 | hi2
-    uint32_t* d_ids = d_docs;
-    uint32_t *d_lo2 = nullptr, *d_hi2 = nullptr;
-    if (!direct) {
-        const uint64_t b_ids = align_up(sum, 64) * 4;
-        SA_TRY(tmp.alloc(b_ids + 2 * nq * 4, s));
-        d_ids = (uint32_t*)tmp.p;
-        d_lo2 = (uint32_t*)((uint8_t*)tmp.p + b_ids);
-        d_hi2 = d_lo2 + nq;
-    }
+    ListSort tmp;   // the ids in rank order, then sorted
+    if (!direct) SA_TRY(tmp.alloc(sum, nq, s));
+    uint32_t* d_ids = direct ? d_docs : tmp.items;
     hipLaunchKernelGGL(k_doc_fill_group, dim3(doc_grid(nq, kBlock / kDocGroup, (uint64_t)c->cus * 16)), dim3(kBlock), 0, s,
                        d_da, d_prev, n, d_lo, d_hi, nq, (const uint64_t*)d_off, d_ids);
     if (n_long)
@@ -508,14 +487,8 @@ static int doc_list_device(sa_context* c, uint64_t n, const uint32_t* d_da, cons
         SA_HIP(host_sync(s));
         return SA_OK;
     }
-    hipLaunchKernelGGL(k_fm_ranges, dim3(fm_grid<1>(nq)), dim3(kBlock), 0, s, (const uint64_t*)d_off, nq, d_lo2, d_hi2);
-    SA_HIP(hipGetLastError());
-    uint64_t got = 0;
     // the ids are any 32-bit words to the sort: key bits for 2^32 values
-    SA_TRY(locate_device_n(c, sum, d_ids, d_lo2, d_hi2, nq, 0, 0, d_off, d_docs, docs_cap, &got, s, 1ull << 32));
-    if (got != sum)
-        return set_err(SA_E_INTERNAL, "doc list: %llu ids sorted of %llu", (unsigned long long)got, (unsigned long long)sum);
-    return SA_OK;
+    return tmp.sort(c, "doc list", "ids", sum, nq, 0, d_off, d_docs, docs_cap, 1ull << 32, s);
 }
 
 // ---- host in, host out, over the steps of sa_host.h ---------------------------
@@ -530,36 +503,6 @@ static int doc_check_offsets(const uint64_t* doc_off, uint64_t D, uint64_t n) {
     if (doc_off[D] != n)
         return set_err(SA_E_INVALID, "doc_off ends at %llu, the text has %llu bytes", (unsigned long long)doc_off[D],
                        (unsigned long long)n);
-    return SA_OK;
-}
-
-// a width-8 array narrowed to 32 bits (entries outside [0, limit] rejected); *src = the 32-bit entries
-static int doc_narrow(const void* a, uint64_t m, int width, uint64_t limit, const char* what,
-                      std::vector<uint32_t>& narrow, const void** src) {
-    *src = a;
-    if (width == 8) {
-        narrow.resize(m);
-        const int64_t* w = (const int64_t*)a;
-        for (uint64_t i = 0; i < m; ++i) {
-            if (w[i] < 0 || (uint64_t)w[i] > limit) return set_err(SA_E_INVALID, "%s entry out of range", what);
-            narrow[i] = (uint32_t)w[i];
-        }
-        *src = narrow.data();
-    }
-    return SA_OK;
-}
-
-// intervals checked as sa_locate checks them, packed lo | hi for one upload
-static int doc_pack_intervals(const uint64_t* lo, const uint64_t* hi, uint64_t nq, uint64_t n, std::vector<uint32_t>& lh) {
-    if (!lo || !hi) return set_err(SA_E_INVALID, "NULL interval array");
-    lh.resize(2 * nq);
-    for (uint64_t q = 0; q < nq; ++q) {
-        if (lo[q] > hi[q] || hi[q] > n)
-            return set_err(SA_E_INVALID, "interval %llu is [%llu, %llu) of %llu", (unsigned long long)q,
-                           (unsigned long long)lo[q], (unsigned long long)hi[q], (unsigned long long)n);
-        lh[q] = (uint32_t)lo[q];
-        lh[nq + q] = (uint32_t)hi[q];
-    }
     return SA_OK;
 }
 
@@ -607,7 +550,7 @@ static int doc_of_host(const uint64_t* doc_off, uint64_t D, uint64_t n, const vo
         return set_err(SA_E_INVALID, "an output may not alias pos or doc_off");
     std::vector<uint32_t> narrow;
     const void* src = nullptr;
-    SA_TRY(doc_narrow(pos, count, width, 0xFFFFFFFFull, "position", narrow, &src));
+    SA_TRY(narrow_u32(pos, count, width, 0xFFFFFFFFull, "position", narrow, &src));
     SA_TRY(need_device());
     std::lock_guard<std::mutex> lk(g_mu);
     DevBuf d_pos, d_off, d_doc, d_rel;
@@ -631,9 +574,8 @@ static int doc_frequency_host(const void* prev, uint64_t n, int width, const uin
     if (nq == 0) return SA_OK;
     if (!df_out) return set_err(SA_E_INVALID, "df_out is NULL");
     std::vector<uint32_t> lh;
-    SA_TRY(doc_pack_intervals(lo, hi, nq, n, lh));
-    if ((const void*)df_out == prev || df_out == lo || df_out == hi)
-        return set_err(SA_E_INVALID, "df_out may not alias an input");
+    SA_TRY(pack_intervals(lo, hi, nq, n, 0, nullptr, lh));
+    SA_TRY(check_no_alias({df_out}, {prev, lo, hi}, "df_out may not alias an input"));
     if (n == 0) {
         std::fill(df_out, df_out + nq, 0ull);
         return SA_OK;
@@ -641,7 +583,7 @@ static int doc_frequency_host(const void* prev, uint64_t n, int width, const uin
     if (!prev) return set_err(SA_E_INVALID, "prev is NULL");
     std::vector<uint32_t> narrow;
     const void* src = nullptr;
-    SA_TRY(doc_narrow(prev, n, width, n, "PRV", narrow, &src));
+    SA_TRY(narrow_u32(prev, n, width, n, "PRV", narrow, &src));
     SA_TRY(need_device());
     std::lock_guard<std::mutex> lk(g_mu);
     DevBuf d_prev, d_lh, d_df;
@@ -661,22 +603,19 @@ static int doc_list_host(const void* da, const void* prev, uint64_t n, int width
     SA_TRY(check_width(width));
     SA_TRY(check_n32(n));
     if (nq > 0xFFFFFFFFull) return set_err(SA_E_INVALID, "nq too large");
-    if (flags & ~(uint32_t)SA_DOC_RANK_ORDER) return set_err(SA_E_INVALID, "unknown flags %#x", flags);
+    SA_TRY(check_flags(flags, SA_DOC_RANK_ORDER));
     if (!off_out) return set_err(SA_E_INVALID, "off_out is NULL");
     off_out[0] = 0;
     if (nq == 0) return SA_OK;
     std::vector<uint32_t> lh;
-    SA_TRY(doc_pack_intervals(lo, hi, nq, n, lh));
+    SA_TRY(pack_intervals(lo, hi, nq, n, 0, nullptr, lh));
     if (n && (!da || !prev)) return set_err(SA_E_INVALID, "da or prev is NULL");
-    if (docs_out && (docs_out == da || docs_out == prev || docs_out == (const void*)lo || docs_out == (const void*)hi ||
-                     docs_out == (const void*)off_out))
-        return set_err(SA_E_INVALID, "docs_out may not alias another array");
-    if ((const void*)off_out == da || (const void*)off_out == prev || off_out == lo || off_out == hi)
-        return set_err(SA_E_INVALID, "off_out may not alias an input");
+    SA_TRY(check_no_alias({docs_out}, {da, prev, lo, hi, off_out}, "docs_out may not alias another array"));
+    SA_TRY(check_no_alias({off_out}, {da, prev, lo, hi}, "off_out may not alias an input"));
     std::vector<uint32_t> nda, nprev;
     const void *sda = nullptr, *sprev = nullptr;
-    SA_TRY(doc_narrow(da, n, width, kDocMaxDocs - 1, "DA", nda, &sda));
-    SA_TRY(doc_narrow(prev, n, width, n, "PRV", nprev, &sprev));
+    SA_TRY(narrow_u32(da, n, width, kDocMaxDocs - 1, "DA", nda, &sda));
+    SA_TRY(narrow_u32(prev, n, width, n, "PRV", nprev, &sprev));
     const uint32_t* p32 = (const uint32_t*)sprev;
     for (uint64_t q = 0; q < nq; ++q) {
         uint64_t df = 0;

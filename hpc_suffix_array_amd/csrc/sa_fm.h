@@ -82,8 +82,8 @@
 // count and the partial-word mask, one backward step, the search, the LF step
 // and the locate walk.  tests/cpp/fm_check.cpp runs them against brute force.
 // Measurements and the resource report: DESIGN.md section 18.  The HIP part
-// needs sa_host.h, sa_find.h (find_pattern), sa_locate.h, sa_mem.h and sa_ibwt.h
-// before it.
+// needs sa_host.h, sa_find.h (find_pattern), sa_locate.h, sa_query.h (mem_block_excl,
+// ListSort) and sa_ibwt.h before it.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -366,7 +366,6 @@ SA_HD uint32_t fm_locate_row(const FmView& v, uint32_t r, const Occ& occ) {
 namespace sa {
 
 static_assert(SA_FM_INFO == kFmInfo && SA_FM_MAX_SAMPLE == kFmMaxSample, "sa_hip.h states them");
-constexpr int kFmHostWord = 3200;                      // host_words: 256 totals, bwt[p] | 8 x 4 bytes of locate's words at + 260
 constexpr uint32_t kFmTileCounters = 2048;             // blocks x cols of a tile of kLfTile rows, in every class
 constexpr uint64_t kFmMaxGrid = 256 * 8;               // 8 workgroups of 256 lanes fill a CU
 static_assert(kLfTile / 64 * 4 == kFmTileCounters && kLfTile / 256 * 16 == kFmTileCounters &&
@@ -540,9 +539,7 @@ static int fm_build_check(const sa_context* c, const uint8_t* d_bwt, uint64_t n,
     if (s && !d_sa) return set_err(SA_E_INVALID, "d_sa is NULL with sa_sample %u", s);
     if (!s && d_sa) return set_err(SA_E_INVALID, "d_sa is given with sa_sample 0");
     if ((uintptr_t)d_sa & 3u) return set_err(SA_E_INVALID, "d_sa is not 4-byte aligned");
-    if (d_index == (const void*)d_bwt || (d_sa && d_index == (const void*)d_sa))
-        return set_err(SA_E_INVALID, "d_index may not alias d_bwt or d_sa");
-    return SA_OK;
+    return check_no_alias({d_index}, {d_bwt, d_sa}, "d_index may not alias d_bwt or d_sa");
 }
 
 static void fm_info_out(const FmHeader& h, uint64_t* info) {
@@ -577,7 +574,8 @@ static int fm_build_device(sa_context* c, const uint8_t* d_bwt, uint64_t n, uint
     hipLaunchKernelGGL(k_lf_hist, dim3(tiles), dim3(kLfBlock), 0, st, d_bwt, n, primary, aligned, d_cnt, tiles);
     hipLaunchKernelGGL(k_lf_scan, dim3(256), dim3(kBlock), 0, st, d_cnt, tiles, d_tot);
     SA_HIP(hipGetLastError());
-    uint32_t* hw = c->host_words + kFmHostWord;
+    static_assert(hw(kHwFmTotals).len == 257, "256 totals and bwt[p]");
+    uint32_t* hw = c->host_words + sa::hw(kHwFmTotals).at;
     hw[256] = 0;
     SA_HIP(hipMemcpyAsync(hw, d_tot, 256 * 4, hipMemcpyDeviceToHost, st));
     SA_HIP(hipMemcpyAsync(hw + 256, d_bwt + primary, 1, hipMemcpyDeviceToHost, st));
@@ -703,15 +701,6 @@ __global__ __launch_bounds__(kBlock) void k_fm_resolve(const void* __restrict__ 
     }
 }
 
-// the materialised hits as an SA of their own: query q owns [off[q], off[q + 1])
-__global__ __launch_bounds__(kBlock) void k_fm_ranges(const uint64_t* __restrict__ off, uint64_t nq,
-                                                      uint32_t* __restrict__ lo2, uint32_t* __restrict__ hi2) {
-    for (uint64_t q = (uint64_t)blockIdx.x * kBlock + threadIdx.x; q < nq; q += (uint64_t)gridDim.x * kBlock) {
-        lo2[q] = (uint32_t)off[q];
-        hi2[q] = (uint32_t)off[q + 1];
-    }
-}
-
 // the checks of sa_fm_locate_device, all before any HIP call
 static int fm_locate_check(const sa_context* c, const void* d_index, const uint32_t* d_lo, const uint32_t* d_hi,
                            uint64_t nq, uint32_t flags, const uint64_t* d_off, const uint64_t* total) {
@@ -723,9 +712,7 @@ static int fm_locate_check(const sa_context* c, const void* d_index, const uint3
     if (!d_hi) return set_err(SA_E_INVALID, "d_hi is NULL");
     if (!d_off) return set_err(SA_E_INVALID, "d_off is NULL");
     if (nq > 0xFFFFFFFFull) return set_err(SA_E_INVALID, "nq too large");
-    if (flags & ~(uint32_t)(SA_LOCATE_SA_ORDER | SA_LOCATE_SMALL_CHUNKS))
-        return set_err(SA_E_INVALID, "unknown flags %#x", flags);
-    return SA_OK;
+    return check_flags(flags, SA_LOCATE_SA_ORDER | SA_LOCATE_SMALL_CHUNKS);
 }
 
 // Host waits: one for the total and the header's words; then sa_locate_device's
@@ -736,7 +723,7 @@ static int fm_locate_device(sa_context* c, const void* d_index, uint64_t index_b
     SA_TRY(fm_locate_check(c, d_index, d_lo, d_hi, nq, flags, d_off, total));
     *total = 0;
     SA_HIP(hipSetDevice(c->device));
-    uint64_t* h = reinterpret_cast<uint64_t*>(c->host_words + kFmHostWord + 260);
+    uint64_t* h = host_u64<kHwFmLocate, 5>(c);
     {
         LocBuf w;
         SA_TRY(w.alloc(32, s));
@@ -760,16 +747,9 @@ static int fm_locate_device(sa_context* c, const void* d_index, uint64_t index_b
     *total = sum;
     if (!d_pos || sum > pos_cap || sum == 0) return SA_OK;
     const bool direct = (flags & SA_LOCATE_SA_ORDER) != 0;
-    LocBuf tmp;   // the hits (4 x total) | lo2 | hi2
-    uint32_t* d_hits = d_pos;
-    uint32_t *d_lo2 = nullptr, *d_hi2 = nullptr;
-    if (!direct) {
-        const uint64_t b_hits = align_up(sum, 64) * 4;
-        SA_TRY(tmp.alloc(b_hits + 2 * nq * 4, s));
-        d_hits = (uint32_t*)tmp.p;
-        d_lo2 = (uint32_t*)((uint8_t*)tmp.p + b_hits);
-        d_hi2 = d_lo2 + nq;
-    }
+    ListSort tmp;   // the hits resolved in SA order, then sorted
+    if (!direct) SA_TRY(tmp.alloc(sum, nq, s));
+    uint32_t* d_hits = direct ? d_pos : tmp.items;
     if (cls == 0)
         hipLaunchKernelGGL((k_fm_resolve<1>), dim3(fm_grid<1>(sum)), dim3(kBlock), 0, s, d_index, index_bytes, d_lo, nq,
                            (const uint64_t*)d_off, sum, d_hits);
@@ -784,13 +764,8 @@ static int fm_locate_device(sa_context* c, const void* d_index, uint64_t index_b
         SA_HIP(host_sync(s));
         return SA_OK;
     }
-    hipLaunchKernelGGL(k_fm_ranges, dim3(fm_grid<1>(nq)), dim3(kBlock), 0, s, (const uint64_t*)d_off, nq, d_lo2, d_hi2);
-    SA_HIP(hipGetLastError());
-    uint64_t got = 0;
-    SA_TRY(locate_device_n(c, sum, d_hits, d_lo2, d_hi2, nq, 0, flags, d_off, d_pos, pos_cap, &got, s, n));
-    if (got != sum)
-        return set_err(SA_E_INTERNAL, "fm locate: %llu hits sorted of %llu", (unsigned long long)got, (unsigned long long)sum);
-    return SA_OK;
+    // the hits as an SA of their own, sorted list by list
+    return tmp.sort(c, "fm locate", "hits", sum, nq, flags, d_off, d_pos, pos_cap, n, s);
 }
 
 // ---- host in, host out, over the steps of sa_host.h -----------------------------
@@ -882,18 +857,12 @@ static int fm_locate_host(const void* index, uint64_t index_bytes, const uint64_
     SA_TRY(fm_host_view(index, index_bytes, h, v));
     if (h.sample == 0) return set_err(SA_E_INVALID, "no samples: the index was built with sa_sample 0");
     if (nq > 0xFFFFFFFFull) return set_err(SA_E_INVALID, "nq too large");
-    if (flags & ~(uint32_t)(SA_LOCATE_SA_ORDER | SA_LOCATE_SMALL_CHUNKS))
-        return set_err(SA_E_INVALID, "unknown flags %#x", flags);
+    SA_TRY(check_flags(flags, SA_LOCATE_SA_ORDER | SA_LOCATE_SMALL_CHUNKS));
     if (!off_out) return set_err(SA_E_INVALID, "off_out is NULL");
     off_out[0] = 0;
     if (nq == 0) return SA_OK;
-    if (!lo || !hi) return set_err(SA_E_INVALID, "NULL interval array");
-    for (uint64_t q = 0; q < nq; ++q) {
-        if (lo[q] > hi[q] || hi[q] > h.n)
-            return set_err(SA_E_INVALID, "interval %llu is [%llu, %llu) of %llu", (unsigned long long)q,
-                           (unsigned long long)lo[q], (unsigned long long)hi[q], (unsigned long long)h.n);
-        off_out[q + 1] = off_out[q] + locate_count(lo[q], hi[q], h.n, max_hits);
-    }
+    std::vector<uint32_t> lh;
+    SA_TRY(pack_intervals(lo, hi, nq, h.n, max_hits, off_out, lh));
     const uint64_t total = off_out[nq];
     if (total > 0xFFFFFFFFull)
         return set_err(SA_E_INVALID, "%llu hits are more than 2^32 - 1: cap it with max_hits", (unsigned long long)total);
@@ -903,11 +872,6 @@ static int fm_locate_host(const void* index, uint64_t index_bytes, const uint64_
     if (total == 0) return SA_OK;
     if (!pos_out) return set_err(SA_E_INVALID, "pos_out is NULL");
     SA_TRY(need_device());
-    std::vector<uint32_t> lh(2 * nq);   // lo | hi, one upload
-    for (uint64_t q = 0; q < nq; ++q) {
-        lh[q] = (uint32_t)lo[q];
-        lh[nq + q] = (uint32_t)hi[q];
-    }
     std::lock_guard<std::mutex> lk(g_mu);
     sa_context* c = nullptr;
     SA_TRY(global_ctx(std::max<uint64_t>(total, 1), &c));

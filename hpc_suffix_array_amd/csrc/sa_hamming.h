@@ -42,13 +42,13 @@
 //                  the hits of piece g = q (k + 1) + j.
 //   k_ham_verify   the hot kernel.  A persistent grid over tiles of kMemTile
 //                  candidates, their pieces from coff by mem_tile_positions
-//                  (sa_mem.h), the rule above by 8-byte words (load8), one
+//                  (sa_query.h), the rule above by 8-byte words (load8), one
 //                  flag byte per lane and a count per tile.  A lane verifies
 //                  the candidates of patterns of up to kHamLaneBytes bytes;
 //                  those of longer patterns go to an LDS list and the
 //                  wavefronts take them one each, 512 bytes a step, the
 //                  mismatches of a step counted by four ballots over the bits
-//                  of the lanes' counts (sa_mem.h's hand-over).
+//                  of the lanes' counts (sa_query.h's mem_wave_turns).
 //                  SA_HAMMING_LANE / SA_HAMMING_WAVE force one path.
 //   scan           scan_i64<ScanSum> over the tile counts; the host reads the
 //                  total (a wait).
@@ -65,8 +65,8 @@
 // The piece bounds, the word count, the validity test and the verify rule
 // compile on the host: tests/cpp/hamming_check.cpp checks them against the
 // sliding-window definition.  Measurements and the resource report: DESIGN.md
-// section 21.  The HIP part needs sa_find.h, sa_locate.h, sa_mem.h and
-// sa_build.hip's scan_i64 before it.
+// section 21.  The HIP part needs sa_find.h, sa_locate.h and sa_query.h
+// (the candidate tiles, CandList, sort_lists) before it.
 #pragma once
 #include <stdint.h>
 
@@ -180,8 +180,6 @@ static_assert(SA_HAMMING_MAX_K == 255 && SA_HAMMING_TOO_MANY == 1 && SA_HAMMING_
 static_assert(kHamMaxK == SA_HAMMING_MAX_K, "the header's largest budget");
 static_assert(kHamLaneBytes % 8 == 0, "whole words");
 
-constexpr int kHamHostWord = 3528;   // host_words: candidates | total (8 bytes each)
-
 __global__ __launch_bounds__(kBlock) void k_ham_pieces(const uint64_t* __restrict__ off, uint64_t nq, uint64_t pat_bytes,
                                                        uint32_t k, uint64_t* __restrict__ poff) {
     const uint64_t k1 = (uint64_t)k + 1u, np = nq * k1;
@@ -196,20 +194,10 @@ __global__ __launch_bounds__(kBlock) void k_ham_pieces(const uint64_t* __restric
 // word[0] += the hits of the pieces, counted as locate_device counts them
 __global__ __launch_bounds__(kBlock) void k_ham_count(const uint32_t* __restrict__ lo, const uint32_t* __restrict__ hi,
                                                       uint64_t np, uint64_t n, unsigned long long* __restrict__ word) {
-    unsigned long long c = 0;
+    unsigned long long c[1] = {0};
     for (uint64_t g = (uint64_t)blockIdx.x * kBlock + threadIdx.x; g < np; g += (uint64_t)gridDim.x * kBlock)
-        c += locate_count(lo[g], hi[g], n, 0);
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) c += __shfl_down(c, o, kWave);
-    __shared__ unsigned long long s_c[kWaves];
-    if (lane_id() == 0) s_c[threadIdx.x / kWave] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        c = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) c += s_c[w];
-        if (c) atomicAdd(word, c);
-    }
+        c[0] += locate_count(lo[g], hi[g], n, 0);
+    block_sum_u64(c, word);
 }
 
 // The patterns and the text as the verify reads them.
@@ -275,7 +263,7 @@ __global__ __launch_bounds__(kBlock) void k_ham_verify(HamIn in, uint32_t k, con
     __shared__ uint32_t s_w[kWaves];
     __shared__ uint64_t s_q[2];
     __shared__ uint32_t s_n;
-    const uint32_t tid = threadIdx.x, lane = lane_id(), wave = tid / kWave;
+    const uint32_t tid = threadIdx.x, lane = lane_id();
     const uint32_t k1 = k + 1u;
     const uint64_t tiles = (total + kMemTile - 1) / kMemTile;
     for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
@@ -302,17 +290,16 @@ __global__ __launch_bounds__(kBlock) void k_ham_verify(HamIn in, uint32_t k, con
             else if (ham_verify_dev<false>(in, k, pa, m, pos[j] - q * k1, h[j]) == kHamKeep) bits |= 1u << j;
         }
         __syncthreads();
-        const uint32_t nl = s_n;   // <= cnt <= kMemTile
-        for (uint32_t x = wave; x < nl; x += kWaves) {
-            const uint32_t slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_list[x]);
-            const uint32_t g = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_pos[slot]);
-            const uint32_t hh = (uint32_t)__builtin_amdgcn_readfirstlane((int)cand[r.s + slot]);
-            const uint32_t q = g / k1;
-            uint64_t pa, m;
-            find_pattern(in.pat_off, q, in.pat_bytes, pa, m);
-            const HamVerdict v = ham_verify_dev<true>(in, k, pa, m, g - q * k1, hh);
-            if (lane == 0 && v == kHamKeep) atomicOr(&s_keep[slot / kMemPer], 1u << (slot % kMemPer));
-        }
+        // s_n <= cnt <= kMemTile
+        mem_wave_turns(
+            s_n, [&](uint32_t x) { return s_list[x]; }, s_pos, cand + r.s,
+            [&](uint32_t, uint32_t slot, uint32_t g, uint32_t hh) {
+                const uint32_t q = g / k1;
+                uint64_t pa, m;
+                find_pattern(in.pat_off, q, in.pat_bytes, pa, m);
+                const HamVerdict v = ham_verify_dev<true>(in, k, pa, m, g - q * k1, hh);
+                if (lane == 0 && v == kHamKeep) atomicOr(&s_keep[slot / kMemPer], 1u << (slot % kMemPer));
+            });
         __syncthreads();
         bits |= s_keep[tid];
         uint32_t sum;
@@ -389,7 +376,7 @@ __global__ __launch_bounds__(kBlock) void k_ham_dist(HamIn in, const uint64_t* _
     __shared__ uint32_t s_w[kWaves];
     __shared__ uint64_t s_q[2];
     __shared__ uint32_t s_n;
-    const uint32_t tid = threadIdx.x, lane = lane_id(), wave = tid / kWave;
+    const uint32_t tid = threadIdx.x, lane = lane_id();
     const uint64_t tiles = (total + kMemTile - 1) / kMemTile;
     for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
         if (tid == 0) s_n = 0u;
@@ -413,19 +400,29 @@ __global__ __launch_bounds__(kBlock) void k_ham_dist(HamIn in, const uint64_t* _
             dist[r.s + slot] = (uint8_t)std::min<uint32_t>(d, kHamMaxK);
         }
         __syncthreads();
-        const uint32_t nl = s_n;
-        for (uint32_t x = wave; x < nl; x += kWaves) {
-            const uint32_t slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_list[x]);
-            const uint32_t q = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_pos[slot]);
-            const uint64_t p = (uint32_t)__builtin_amdgcn_readfirstlane((int)pos_out[r.s + slot]);
-            uint64_t pa, m;
-            find_pattern(in.pat_off, q, in.pat_bytes, pa, m);
-            uint32_t d = 0;
-            if (p < in.n && m <= in.n - p) d = ham_count_wave(in, pa, p, 0, m, kHamMaxK);
-            if (lane == 0) dist[r.s + slot] = (uint8_t)std::min<uint32_t>(d, kHamMaxK);
-        }
+        mem_wave_turns(
+            s_n, [&](uint32_t x) { return s_list[x]; }, s_pos, pos_out + r.s,
+            [&](uint32_t, uint32_t slot, uint32_t q, uint32_t p) {
+                uint64_t pa, m;
+                find_pattern(in.pat_off, q, in.pat_bytes, pa, m);
+                uint32_t d = 0;
+                if (p < in.n && m <= in.n - p) d = ham_count_wave(in, pa, p, 0, m, kHamMaxK);
+                if (lane == 0) dist[r.s + slot] = (uint8_t)std::min<uint32_t>(d, kHamMaxK);
+            });
         __syncthreads();   // the next tile writes these arrays
     }
+}
+
+static int ham_check_sizes(uint64_t nq, uint64_t k) {
+    if (nq > 0xFFFFFFFFull) return set_err(SA_E_INVALID, "nq too large");
+    if (k > SA_HAMMING_MAX_K) return set_err(SA_E_INVALID, "k is above SA_HAMMING_MAX_K = %d", SA_HAMMING_MAX_K);
+    if (nq * (k + 1) > 0xFFFFFFFFull)
+        return set_err(SA_E_INVALID, "nq (k + 1) = %llu pieces are more than 2^32 - 1", (unsigned long long)(nq * (k + 1)));
+    return SA_OK;
+}
+static int ham_check_flags(uint32_t flags) {
+    SA_TRY(check_flags(flags, SA_HAMMING_LANE | SA_HAMMING_WAVE));
+    return check_exclusive(flags, SA_HAMMING_LANE, SA_HAMMING_WAVE, "SA_HAMMING_LANE", "SA_HAMMING_WAVE");
 }
 
 // the checks of sa_hamming_device, all before any HIP call
@@ -437,27 +434,15 @@ static int ham_check_args(const sa_context* c, const uint8_t* d_text, uint64_t n
     if (!info) return set_err(SA_E_INVALID, "info is NULL");
     if (!d_off) return set_err(SA_E_INVALID, "d_off is NULL");
     if (n > 0xFFFFFFFFull) return set_err(SA_E_INVALID, "n too large");
-    if (nq > 0xFFFFFFFFull) return set_err(SA_E_INVALID, "nq too large");
-    if (k > SA_HAMMING_MAX_K) return set_err(SA_E_INVALID, "k is above SA_HAMMING_MAX_K = %d", SA_HAMMING_MAX_K);
-    if (nq * (k + 1) > 0xFFFFFFFFull)
-        return set_err(SA_E_INVALID, "nq (k + 1) = %llu pieces are more than 2^32 - 1", (unsigned long long)(nq * (k + 1)));
+    SA_TRY(ham_check_sizes(nq, k));
     if (n && !d_text) return set_err(SA_E_INVALID, "d_text is NULL");
     if (n && !d_sa) return set_err(SA_E_INVALID, "d_sa is NULL");
     if (pat_bytes && !d_pat) return set_err(SA_E_INVALID, "d_pat is NULL");
     if (nq && !d_pat_off) return set_err(SA_E_INVALID, "d_pat_off is NULL");
-    if (flags & ~(uint32_t)(SA_HAMMING_LANE | SA_HAMMING_WAVE)) return set_err(SA_E_INVALID, "unknown flags %#x", flags);
-    if (flags == (SA_HAMMING_LANE | SA_HAMMING_WAVE))
-        return set_err(SA_E_INVALID, "SA_HAMMING_LANE and SA_HAMMING_WAVE exclude each other");
+    SA_TRY(ham_check_flags(flags));
     if (d_dist && !d_pos) return set_err(SA_E_INVALID, "d_dist without d_pos");
-    const void* in[4] = {d_text, d_sa, d_pat, d_pat_off};
-    const void* out[3] = {d_off, d_pos, d_dist};
-    for (const void* o : out)
-        for (const void* i : in)
-            if (o && o == i) return set_err(SA_E_INVALID, "an output aliases an input");
-    if ((d_pos && (const void*)d_pos == (const void*)d_off) || (d_dist && (const void*)d_dist == (const void*)d_off) ||
-        (d_dist && (const void*)d_dist == (const void*)d_pos))
-        return set_err(SA_E_INVALID, "two outputs are one buffer");
-    return SA_OK;
+    SA_TRY(check_no_alias({d_off, d_pos, d_dist}, {d_text, d_sa, d_pat, d_pat_off}));
+    return check_distinct({d_off, d_pos, d_dist});
 }
 
 // the host form's outputs, allocated when the total is known
@@ -479,20 +464,13 @@ static int hamming_device(sa_context* c, const uint8_t* d_text, uint64_t n, cons
     info[0] = info[1] = 0;
     info[2] = np;
     SA_HIP(hipSetDevice(c->device));
-    auto no_hits = [&]() -> int {
-        SA_HIP(hipMemsetAsync(d_off, 0, (nq + 1) * 8, s));
-        SA_HIP(host_sync(s));
-        return SA_OK;
-    };
-    if (nq == 0 || n == 0) return no_hits();
-    uint64_t* h = reinterpret_cast<uint64_t*>(c->host_words + kHamHostWord);
+    if (nq == 0 || n == 0) return empty_csr(d_off, nq, s);
+    uint64_t* h = host_u64<kHwHamming, 2>(c);
     // no byte of an empty buffer is read (load8 ends at pat_bytes): any pointer serves
     const HamIn in{d_text, n, d_pat ? d_pat : d_text, pat_bytes, d_pat_off};
     const uint32_t kk = (uint32_t)k;
     const uint32_t pgrid = (uint32_t)std::min<uint64_t>((np + kBlock) / kBlock, (uint64_t)c->cus * 8);
-    uint64_t cands = 0;
-    LocBuf list;   // coff (np + 1) | tile counts | candidates | flag bytes | lo2 | hi2
-    uint64_t* d_coff = nullptr;
+    CandList list;   // extra: lo2 | hi2
     {
         LocBuf seeds;   // the candidate count (16 bytes) | piece offsets (np + 1) | lo | hi
         SA_TRY(seeds.alloc(16 + (np + 1) * 8 + 2 * np * 4, s));
@@ -509,42 +487,22 @@ static int hamming_device(sa_context* c, const uint8_t* d_text, uint64_t n, cons
         SA_HIP(hipGetLastError());
         SA_HIP(hipMemcpyAsync(h, d_word, 8, hipMemcpyDeviceToHost, s));
         SA_HIP(host_sync(s));
-        cands = h[0];
-        info[1] = cands;
+        info[1] = h[0];
         SA_TRACE("hamming: nq %llu k %u pieces %llu candidates %llu", (unsigned long long)nq, kk, (unsigned long long)np,
-                 (unsigned long long)cands);
-        if (max_candidates && cands > max_candidates) {
-            SA_TRY(no_hits());
-            return SA_HAMMING_TOO_MANY;
-        }
-        if (cands == 0) return no_hits();
-        const uint64_t tiles = (cands + kMemTile - 1) / kMemTile;
-        SA_TRY(list.alloc((np + 1) * 8 + tiles * 8 + align_up(cands, 4) * 4 + align_up(tiles * kBlock, 4) + 2 * nq * 4, s));
-        d_coff = (uint64_t*)list.p;
-        uint32_t* d_cand = (uint32_t*)(d_coff + np + 1 + tiles);
-        uint64_t got = 0;
-        SA_TRY(locate_device(c, n, d_sa, d_lo, d_hi, np, 0, SA_LOCATE_SA_ORDER, d_coff, d_cand, cands, &got, s));
-        if (got != cands)
-            return set_err(SA_E_INTERNAL, "hamming: locate wrote %llu hits for %llu candidates", (unsigned long long)got,
-                           (unsigned long long)cands);
+                 (unsigned long long)h[0]);
+        const int rc = list.fill(c, "hamming", n, d_sa, d_lo, d_hi, np, h[0], max_candidates, SA_HAMMING_TOO_MANY,
+                                 d_off, nq, SA_LOCATE_SA_ORDER, 2 * nq * 4, s);
+        if (rc || !list.tiles) return rc;
     }
-    const uint64_t tiles = (cands + kMemTile - 1) / kMemTile;
-    int64_t* d_tcnt = (int64_t*)(d_coff + np + 1);
-    const uint32_t* d_cand = (const uint32_t*)(d_tcnt + tiles);
-    uint8_t* d_flagb = (uint8_t*)(d_cand + align_up(cands, 4));
-    uint32_t* d_lo2 = (uint32_t*)(d_flagb + align_up(tiles * kBlock, 4));
-    uint32_t* d_hi2 = d_lo2 + nq;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(tiles, (uint64_t)c->cus * kMemGridPerCu);
+    uint32_t *d_lo2 = (uint32_t*)list.extra, *d_hi2 = d_lo2 + nq;
     const uint64_t lane_bytes = flags & SA_HAMMING_LANE ? ~0ull : flags & SA_HAMMING_WAVE ? 0ull : kHamLaneBytes;
-    hipLaunchKernelGGL(k_ham_verify, dim3(grid), dim3(kBlock), 0, s, in, kk, (const uint64_t*)d_coff, np, d_cand, cands,
-                       lane_bytes, d_flagb, d_tcnt);
+    hipLaunchKernelGGL(k_ham_verify, dim3(list.grid), dim3(kBlock), 0, s, in, kk, (const uint64_t*)list.coff, np,
+                       (const uint32_t*)list.cand, list.cands, lane_bytes, list.flagb, list.tcnt);
     SA_HIP(hipGetLastError());
-    SA_TRY(scan_i64<ScanSum>(d_tcnt, tiles, s));
-    SA_HIP(hipMemcpyAsync(h + 1, d_tcnt + (tiles - 1), 8, hipMemcpyDeviceToHost, s));
-    SA_HIP(host_sync(s));
-    const uint64_t total = h[1];
-    info[0] = total;
-    if (total == 0) return no_hits();
+    SA_TRY(list.scan(s));
+    SA_TRY(list.total(h + 1, s, &info[0]));
+    const uint64_t total = info[0];
+    if (total == 0) return empty_csr(d_off, nq, s);
     if (total > 0xFFFFFFFFull)
         return set_err(SA_E_INVALID, "%llu occurrences are more than 2^32 - 1: search fewer patterns a call",
                        (unsigned long long)total);
@@ -561,16 +519,13 @@ static int hamming_device(sa_context* c, const uint8_t* d_text, uint64_t n, cons
     const bool write = d_pos != nullptr && total <= out_cap;
     LocBuf surv;   // the starts of the kept candidates, in candidate order
     if (write) SA_TRY(surv.alloc(align_up(total, 4) * 4, s));
-    hipLaunchKernelGGL(k_ham_emit, dim3(grid), dim3(kBlock), 0, s, in, kk, (const uint64_t*)d_coff, np, d_cand, cands,
-                       (const uint8_t*)d_flagb, (const int64_t*)d_tcnt, (uint32_t*)surv.p, d_lo2, d_hi2);
+    hipLaunchKernelGGL(k_ham_emit, dim3(list.grid), dim3(kBlock), 0, s, in, kk, (const uint64_t*)list.coff, np,
+                       (const uint32_t*)list.cand, list.cands, (const uint8_t*)list.flagb, (const int64_t*)list.tcnt,
+                       (uint32_t*)surv.p, d_lo2, d_hi2);
     SA_HIP(hipGetLastError());
-    uint64_t got = 0;
-    // the sizing call: the counts alone, from lo2 / hi2 (nothing is gathered, d_cand stands in)
-    SA_TRY(locate_device_n(c, total, write ? (const uint32_t*)surv.p : d_cand, d_lo2, d_hi2, nq, 0, 0, d_off,
-                           write ? d_pos : nullptr, out_cap, &got, s, n));
-    if (got != total)
-        return set_err(SA_E_INTERNAL, "hamming: %llu occurrences sorted of %llu", (unsigned long long)got,
-                       (unsigned long long)total);
+    // the sizing call: the counts alone, from lo2 / hi2 (nothing is gathered, the candidates stand in)
+    SA_TRY(sort_lists(c, "hamming", "occurrences", total, write ? (const uint32_t*)surv.p : list.cand, d_lo2, d_hi2, nq,
+                      0, d_off, write ? d_pos : nullptr, out_cap, n, s));
     if (write && d_dist) {
         const uint64_t otiles = (total + kMemTile - 1) / kMemTile;
         const uint32_t ogrid = (uint32_t)std::min<uint64_t>(otiles, (uint64_t)c->cus * kMemGridPerCu);
@@ -591,30 +546,19 @@ static int hamming_host(const uint8_t* text, uint64_t n, const void* sa, int sa_
     if (!info) return set_err(SA_E_INVALID, "info is NULL");
     if (!off_out) return set_err(SA_E_INVALID, "off_out is NULL");
     SA_TRY(check_n32(n));
-    if (nq > 0xFFFFFFFFull) return set_err(SA_E_INVALID, "nq too large");
-    if (k > SA_HAMMING_MAX_K) return set_err(SA_E_INVALID, "k is above SA_HAMMING_MAX_K = %d", SA_HAMMING_MAX_K);
-    if (nq * (k + 1) > 0xFFFFFFFFull)
-        return set_err(SA_E_INVALID, "nq (k + 1) = %llu pieces are more than 2^32 - 1", (unsigned long long)(nq * (k + 1)));
+    SA_TRY(ham_check_sizes(nq, k));
     if (n && !text) return set_err(SA_E_INVALID, "text is NULL");
     if (n && !sa) return set_err(SA_E_INVALID, "sa is NULL");
     if (nq && !pat_off) return set_err(SA_E_INVALID, "pat_off is NULL");
-    if (flags & ~(uint32_t)(SA_HAMMING_LANE | SA_HAMMING_WAVE)) return set_err(SA_E_INVALID, "unknown flags %#x", flags);
-    if (flags == (SA_HAMMING_LANE | SA_HAMMING_WAVE))
-        return set_err(SA_E_INVALID, "SA_HAMMING_LANE and SA_HAMMING_WAVE exclude each other");
+    SA_TRY(ham_check_flags(flags));
     if (dist_out && !pos_out) return set_err(SA_E_INVALID, "dist_out without pos_out");
     for (uint64_t q = 0; q < nq; ++q)
         if (pat_off[q] > pat_off[q + 1])
             return set_err(SA_E_INVALID, "pattern offsets decrease at %llu", (unsigned long long)q);
     const uint64_t pat_bytes = nq ? pat_off[nq] : 0;
     if (pat_bytes && !pat) return set_err(SA_E_INVALID, "pat is NULL");
-    const void* in[4] = {text, sa, pat, pat_off};
-    const void* out[3] = {off_out, pos_out, dist_out};
-    for (const void* o : out)
-        for (const void* i : in)
-            if (o && o == i) return set_err(SA_E_INVALID, "an output aliases an input");
-    if ((pos_out && pos_out == (void*)off_out) || (dist_out && (void*)dist_out == (void*)off_out) ||
-        (dist_out && (void*)dist_out == pos_out))
-        return set_err(SA_E_INVALID, "two outputs are one buffer");
+    SA_TRY(check_no_alias({off_out, pos_out, dist_out}, {text, sa, pat, pat_off}));
+    SA_TRY(check_distinct({off_out, pos_out, dist_out}));
     std::vector<uint32_t> narrow;
     const void* src = nullptr;
     SA_TRY(narrow_sa(sa, n, sa_width, narrow, &src));

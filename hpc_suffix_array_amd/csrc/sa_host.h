@@ -169,25 +169,48 @@ static int check_width(int sa_width) {
     return sa_width == 4 || sa_width == 8 ? SA_OK : set_err(SA_E_INVALID, "sa_width must be 4 or 8");
 }
 static int check_n32(uint64_t n) { return n > 0xFFFFFFFFull ? set_err(SA_E_INVALID, "n too large") : SA_OK; }
+static int check_flags(uint32_t flags, uint32_t known) {
+    return (flags & ~known) ? set_err(SA_E_INVALID, "unknown flags %#x", flags) : SA_OK;
+}
+static int check_exclusive(uint32_t flags, uint32_t a, uint32_t b, const char* name_a, const char* name_b) {
+    return (flags & a) && (flags & b) ? set_err(SA_E_INVALID, "%s and %s exclude each other", name_a, name_b) : SA_OK;
+}
+// no output is an input; a NULL output is one the caller left out
+static int check_no_alias(std::initializer_list<const void*> outs, std::initializer_list<const void*> ins,
+                          const char* msg = "an output aliases an input") {
+    for (const void* o : outs)
+        for (const void* i : ins)
+            if (o && o == i) return set_err(SA_E_INVALID, "%s", msg);
+    return SA_OK;
+}
+static int check_distinct(std::initializer_list<const void*> outs, const char* msg = "two outputs are one buffer") {
+    for (const void* const* a = outs.begin(); a != outs.end(); ++a)
+        for (const void* const* b = outs.begin(); b != a; ++b)
+            if (*a && *a == *b) return set_err(SA_E_INVALID, "%s", msg);
+    return SA_OK;
+}
 // the forms that take no context ask for the device themselves, after every argument check
 static int need_device() {
     return sa_device_count() > 0 ? SA_OK : set_err(SA_E_HIP, "no HIP device visible (libsa_hip needs an MI355X)");
 }
 
-// a width-8 SA narrowed to 32 bits (entries outside [0, n) rejected);
-// *src = the 32-bit entries
-static int narrow_sa(const void* sa, uint64_t n, int sa_width, std::vector<uint32_t>& narrow, const void** src) {
-    *src = sa;
-    if (sa_width == 8) {
-        narrow.resize(n);
-        const int64_t* w = (const int64_t*)sa;
-        for (uint64_t i = 0; i < n; ++i) {
-            if (w[i] < 0 || (uint64_t)w[i] >= n) return set_err(SA_E_INVALID, "SA entry out of range");
+// a width-8 array of m entries narrowed to 32 bits (entries outside [0, limit] rejected); *src = the 32-bit entries
+static int narrow_u32(const void* a, uint64_t m, int width, uint64_t limit, const char* what,
+                      std::vector<uint32_t>& narrow, const void** src) {
+    *src = a;
+    if (width == 8) {
+        narrow.resize(m);
+        const int64_t* w = (const int64_t*)a;
+        for (uint64_t i = 0; i < m; ++i) {
+            if (w[i] < 0 || (uint64_t)w[i] > limit) return set_err(SA_E_INVALID, "%s entry out of range", what);
             narrow[i] = (uint32_t)w[i];
         }
         *src = narrow.data();
     }
     return SA_OK;
+}
+static int narrow_sa(const void* sa, uint64_t n, int sa_width, std::vector<uint32_t>& narrow, const void** src) {
+    return narrow_u32(sa, n, sa_width, n - 1, "SA", narrow, src);   // n == 0: no entry is looked at
 }
 
 // a device allocation freed by its scope (the sizes are the caller's: the

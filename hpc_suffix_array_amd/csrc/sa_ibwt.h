@@ -89,7 +89,7 @@
 // splitter predicate and directory, both walks with the byte packing, the
 // jump and the verdict.  tests/cpp/ibwt_check.cpp runs them against brute
 // force.  Measurements and the resource report: DESIGN.md section 17.  The HIP
-// part needs sa_host.h, sa_locate.h (LocBuf), sa_mem.h (mem_block_excl) and
+// part needs sa_host.h, sa_locate.h (LocBuf), sa_query.h (mem_block_excl) and
 // sa_build.hip's scan_i64 before it.
 #pragma once
 #include <stdint.h>
@@ -234,7 +234,6 @@ constexpr int kLfBlock = 1024;                                  // lanes of an L
 constexpr int kLfWaves = kLfBlock / kWave;                      // 16
 constexpr uint32_t kLfWaveRanks = kLfTile / kLfWaves;           // 2048 ranks per wavefront
 constexpr uint32_t kLfStep = 4 * kWave;                         // 256 ranks a step: one dword per lane
-constexpr int kIbwtHostWord = 3104;                             // host_words: 4 x 8 bytes of info
 constexpr int kIbwtDevInfo = 4;                                 // device info words: splitters, longest, L, unused
 static_assert(kLfWaveRanks % kLfStep == 0 && kIbwtTileWords == (uint32_t)kBlock, "whole steps; a lane per word");
 
@@ -545,8 +544,7 @@ static int ibwt_check_args(const sa_context* c, const uint8_t* d_bwt, uint64_t n
     if (!d_text) return set_err(SA_E_INVALID, "d_text is NULL");
     if (primary >= n) return set_err(SA_E_INVALID, "primary index %llu is not below n", (unsigned long long)primary);
     if (d_text == d_bwt) return set_err(SA_E_INVALID, "d_text may not alias d_bwt");
-    if (d_sa && ((const void*)d_sa == (const void*)d_bwt || (const void*)d_sa == (const void*)d_text))
-        return set_err(SA_E_INVALID, "d_sa may not alias d_bwt or d_text");
+    SA_TRY(check_no_alias({d_sa}, {d_bwt, d_text}, "d_sa may not alias d_bwt or d_text"));
     if ((uintptr_t)d_sa & 3u) return set_err(SA_E_INVALID, "d_sa is not 4-byte aligned");
     return SA_OK;
 }
@@ -594,7 +592,7 @@ static int ibwt_device(sa_context* c, const uint8_t* d_bwt, uint64_t n, uint64_t
     hipLaunchKernelGGL(k_ibwt_walk2, dim3(tiles), dim3(kBlock), 0, s, lf, p, n, dir, (const uint64_t*)d_na,
                        (const uint32_t*)d_first, (const unsigned long long*)d_info, IbwtOut{d_text, d_sa});
     SA_HIP(hipGetLastError());
-    uint64_t* h = reinterpret_cast<uint64_t*>(c->host_words + kIbwtHostWord);
+    uint64_t* h = host_u64<kHwIbwt, kIbwtDevInfo>(c);
     SA_HIP(hipMemcpyAsync(h, d_info, b_info, hipMemcpyDeviceToHost, s));
     SA_HIP(host_sync(s));
     SA_TRACE("ibwt: %llu splitters (cap %llu), longest sublist %llu, cycle of r0 %llu of %llu", (unsigned long long)h[0],
@@ -642,8 +640,7 @@ static int ibwt_host(const uint8_t* bwt, uint64_t n, uint64_t primary, uint8_t* 
     if (!bwt || !text_out) return set_err(SA_E_INVALID, "NULL host pointer");
     if (primary >= n) return set_err(SA_E_INVALID, "primary index %llu is not below n", (unsigned long long)primary);
     if (text_out == bwt) return set_err(SA_E_INVALID, "text_out may not alias bwt");
-    if (sa_out && (sa_out == (const void*)bwt || sa_out == (const void*)text_out))
-        return set_err(SA_E_INVALID, "sa_out may not alias bwt or text_out");
+    SA_TRY(check_no_alias({sa_out}, {bwt, text_out}, "sa_out may not alias bwt or text_out"));
     SA_TRY(need_device());
     std::lock_guard<std::mutex> lk(g_mu);
     sa_context* c = nullptr;

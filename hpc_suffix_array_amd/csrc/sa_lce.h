@@ -515,7 +515,7 @@ static int lcp_min_host(const void* lcp, uint64_t n, int width, const uint64_t* 
     if (nq == 0) return SA_OK;
     if (!lo || !hi) return set_err(SA_E_INVALID, "NULL interval array");
     if (!out) return set_err(SA_E_INVALID, "out is NULL");
-    if ((const void*)out == lcp || out == lo || out == hi) return set_err(SA_E_INVALID, "out may not alias an input");
+    SA_TRY(check_no_alias({out}, {lcp, lo, hi}, "out may not alias an input"));
     if (n && !lcp) return set_err(SA_E_INVALID, "lcp is NULL");
     std::vector<uint32_t> narrow;
     const void* src = nullptr;
@@ -559,9 +559,7 @@ static int lce_positions_host(bool order, const uint8_t* text, uint64_t n, const
     if (!i || !j) return set_err(SA_E_INVALID, "NULL position array");
     if (order && (!li || !lj)) return set_err(SA_E_INVALID, "NULL length array");
     if (!out) return set_err(SA_E_INVALID, "out is NULL");
-    if (out == (const void*)i || out == (const void*)j || out == (const void*)li || out == (const void*)lj ||
-        out == (const void*)text || out == sa)
-        return set_err(SA_E_INVALID, "out may not alias an input");
+    SA_TRY(check_no_alias({out}, {i, j, li, lj, text, sa}, "out may not alias an input"));
     if (n && (!text || !sa)) return set_err(SA_E_INVALID, "NULL host pointer");
     std::vector<uint32_t> narrow;
     const void* src = nullptr;

@@ -169,7 +169,6 @@ constexpr uint32_t kLocRankMax = 64;                     // longest segment rank
 constexpr uint32_t kLocGridPerCu = 4;                    // workgroups per CU of the persistent grid
 constexpr uint64_t kLocateSortMax = 1ull << 28;          // large hits sorted in one call
 constexpr uint64_t kLocateTestChunk = 1ull << 14;        // SA_LOCATE_SMALL_CHUNKS
-constexpr int kLocHostWord = 3072;                       // host_words: total, n_large, large hits (3 x 8 bytes)
 static_assert(kLocPer == 16 && kLocSlots <= 65536, "16 slots per lane, 16-bit slot numbers");
 
 typedef uint32_t loc_u32x4 __attribute__((ext_vector_type(4), aligned(4)));
@@ -448,6 +447,13 @@ struct LocBuf {
     }
 };
 
+// the empty answer in CSR form: rows + 1 zero offsets, waited for
+static int empty_csr(uint64_t* d_off, uint64_t rows, hipStream_t s) {
+    SA_HIP(hipMemsetAsync(d_off, 0, (rows + 1) * 8, s));
+    SA_HIP(host_sync(s));
+    return SA_OK;
+}
+
 // the checks of sa_locate_device, all before any HIP call
 static int locate_check_args(const sa_context* c, uint64_t n, const uint32_t* d_sa, const uint32_t* d_lo,
                              const uint32_t* d_hi, uint64_t nq, uint32_t flags, const uint64_t* d_off,
@@ -461,9 +467,7 @@ static int locate_check_args(const sa_context* c, uint64_t n, const uint32_t* d_
     if (n > 0xFFFFFFFFull) return set_err(SA_E_INVALID, "n too large");
     if (nq > 0xFFFFFFFFull) return set_err(SA_E_INVALID, "nq too large");
     if (d_pos && (const void*)d_pos == (const void*)d_sa) return set_err(SA_E_INVALID, "d_pos may not alias d_sa");
-    if (flags & ~(uint32_t)(SA_LOCATE_SA_ORDER | SA_LOCATE_SMALL_CHUNKS))
-        return set_err(SA_E_INVALID, "unknown flags %#x", flags);
-    return SA_OK;
+    return check_flags(flags, SA_LOCATE_SA_ORDER | SA_LOCATE_SMALL_CHUNKS);
 }
 
 // Host waits: one when no query is large (or nothing is written); with large
@@ -477,12 +481,8 @@ static int locate_device_n(sa_context* c, uint64_t n, const uint32_t* d_sa, cons
     SA_TRY(locate_check_args(c, n, d_sa, d_lo, d_hi, nq, flags, d_off, d_pos, total));
     *total = 0;
     SA_HIP(hipSetDevice(c->device));
-    if (nq == 0) {
-        SA_HIP(hipMemsetAsync(d_off, 0, 8, s));
-        SA_HIP(host_sync(s));
-        return SA_OK;
-    }
-    uint64_t* h = reinterpret_cast<uint64_t*>(c->host_words + kLocHostWord);
+    if (nq == 0) return empty_csr(d_off, 0, s);
+    uint64_t* h = host_u64<kHwLocate, 3>(c);
     {
         LocBuf w;
         SA_TRY(w.alloc(16, s));
@@ -585,6 +585,23 @@ static int locate_device(sa_context* c, uint64_t n, const uint32_t* d_sa, const 
     return locate_device_n(c, n, d_sa, d_lo, d_hi, nq, max_hits, flags, d_off, d_pos, pos_cap, total, s, n);
 }
 
+// the host forms' intervals checked against [0, n] and packed lo | hi for one upload;
+// off_out (when given, off_out[0] = 0) takes the sums of their hits under max_hits
+static int pack_intervals(const uint64_t* lo, const uint64_t* hi, uint64_t nq, uint64_t n, uint64_t max_hits,
+                          uint64_t* off_out, std::vector<uint32_t>& lh) {
+    if (!lo || !hi) return set_err(SA_E_INVALID, "NULL interval array");
+    lh.resize(2 * nq);
+    for (uint64_t q = 0; q < nq; ++q) {
+        if (lo[q] > hi[q] || hi[q] > n)
+            return set_err(SA_E_INVALID, "interval %llu is [%llu, %llu) of %llu", (unsigned long long)q,
+                           (unsigned long long)lo[q], (unsigned long long)hi[q], (unsigned long long)n);
+        if (off_out) off_out[q + 1] = off_out[q] + locate_count(lo[q], hi[q], n, max_hits);
+        lh[q] = (uint32_t)lo[q];
+        lh[nq + q] = (uint32_t)hi[q];
+    }
+    return SA_OK;
+}
+
 // host in, host out (sa_locate), over the steps of sa_host.h: the offsets and
 // the total are the host's own
 static int locate_host(const void* sa, uint64_t n, int sa_width, const uint64_t* lo, const uint64_t* hi, uint64_t nq,
@@ -592,18 +609,12 @@ static int locate_host(const void* sa, uint64_t n, int sa_width, const uint64_t*
     SA_TRY(check_width(sa_width));
     SA_TRY(check_n32(n));
     if (nq > 0xFFFFFFFFull) return set_err(SA_E_INVALID, "nq too large");
-    if (flags & ~(uint32_t)(SA_LOCATE_SA_ORDER | SA_LOCATE_SMALL_CHUNKS))
-        return set_err(SA_E_INVALID, "unknown flags %#x", flags);
+    SA_TRY(check_flags(flags, SA_LOCATE_SA_ORDER | SA_LOCATE_SMALL_CHUNKS));
     if (!off_out) return set_err(SA_E_INVALID, "off_out is NULL");
     off_out[0] = 0;
     if (nq == 0) return SA_OK;
-    if (!lo || !hi) return set_err(SA_E_INVALID, "NULL interval array");
-    for (uint64_t q = 0; q < nq; ++q) {
-        if (lo[q] > hi[q] || hi[q] > n)
-            return set_err(SA_E_INVALID, "interval %llu is [%llu, %llu) of %llu", (unsigned long long)q,
-                           (unsigned long long)lo[q], (unsigned long long)hi[q], (unsigned long long)n);
-        off_out[q + 1] = off_out[q] + locate_count(lo[q], hi[q], n, max_hits);
-    }
+    std::vector<uint32_t> lh;
+    SA_TRY(pack_intervals(lo, hi, nq, n, max_hits, off_out, lh));
     const uint64_t total = off_out[nq];
     if (pos_cap < total)
         return set_err(SA_E_INVALID, "pos_cap %llu is below the %llu hits", (unsigned long long)pos_cap,
@@ -615,11 +626,6 @@ static int locate_host(const void* sa, uint64_t n, int sa_width, const uint64_t*
     if (total == 0) return SA_OK;
     if (!pos_out) return set_err(SA_E_INVALID, "pos_out is NULL");
     SA_TRY(need_device());
-    std::vector<uint32_t> lh(2 * nq);   // lo | hi, one upload
-    for (uint64_t q = 0; q < nq; ++q) {
-        lh[q] = (uint32_t)lo[q];
-        lh[nq + q] = (uint32_t)hi[q];
-    }
     std::lock_guard<std::mutex> lk(g_mu);
     sa_context* c = nullptr;
     SA_TRY(global_ctx(std::max<uint64_t>(n, 1), &c));

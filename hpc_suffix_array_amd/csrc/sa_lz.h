@@ -72,7 +72,7 @@
 // The walks, next(), the jump and reach steps compile on the host:
 // tests/cpp/lz_check.cpp checks them against the O(n^2) definition and the
 // serial parse.  Measurements and the resource report: DESIGN.md section 15.
-// The HIP part needs sa_host.h, sa_locate.h (LocBuf), sa_mem.h
+// The HIP part needs sa_host.h, sa_locate.h (LocBuf), sa_query.h
 // (mem_block_excl) and sa_build.hip's scan_i64 and lcp_device before it.
 #pragma once
 #include <stdint.h>
@@ -312,7 +312,6 @@ static_assert(kLzTile == kLzFan * kLzFan && kLzTile == (uint32_t)kTile && kLzFan
               "a tile is two levels; a wavefront reduces one node");
 constexpr int kLzPer = (int)(kLzTile / kBlock);   // 16 entries per lane
 constexpr int kLzRounds = 12;                     // 2^12 = kLzTile hops
-constexpr int kLzHostWord = 3088;                 // host_words: z (8 bytes)
 static_assert((1u << kLzRounds) == kLzTile && kLzPer == 16, "one uint16 of path bits per lane");
 
 // the global hierarchy: level 0 is (sa, lcp), level k >= 1 is node[k]
@@ -607,12 +606,8 @@ static int lpf_check_args(const sa_context* c, const uint8_t* d_text, uint64_t n
     if (!d_text && !d_lcp) return set_err(SA_E_INVALID, "d_text and d_lcp are both NULL");
     if ((uintptr_t)d_lpf & 3u) return set_err(SA_E_INVALID, "d_lpf is not 4-byte aligned");
     if ((uintptr_t)d_src & 3u) return set_err(SA_E_INVALID, "d_src is not 4-byte aligned");
-    const void* in[3] = {d_text, d_sa, d_lcp};
-    for (const void* i : in)
-        if (i && (i == (const void*)d_lpf || i == (const void*)d_src))
-            return set_err(SA_E_INVALID, "an output aliases an input");
-    if (d_lpf == d_src) return set_err(SA_E_INVALID, "two outputs are one buffer");
-    return SA_OK;
+    SA_TRY(check_no_alias({d_lpf, d_src}, {d_text, d_sa, d_lcp}));
+    return check_distinct({d_lpf, d_src});
 }
 
 static int lpf_device(sa_context* c, const uint8_t* d_text, uint64_t n, const uint32_t* d_sa, const uint32_t* d_lcp,
@@ -672,12 +667,8 @@ static int lz77_check_args(const sa_context* c, uint64_t n, const uint32_t* d_lp
     if (given) {
         if (((uintptr_t)d_pos | (uintptr_t)d_len | (uintptr_t)d_fsrc) & 3u)
             return set_err(SA_E_INVALID, "an output is not 4-byte aligned");
-        const void* out[3] = {d_pos, d_len, d_fsrc};
-        for (const void* o : out)
-            if (o == (const void*)d_lpf || o == (const void*)d_src)
-                return set_err(SA_E_INVALID, "an output aliases an input");
-        if (d_pos == d_len || d_pos == d_fsrc || d_len == d_fsrc)
-            return set_err(SA_E_INVALID, "two outputs are one buffer");
+        SA_TRY(check_no_alias({d_pos, d_len, d_fsrc}, {d_lpf, d_src}));
+        SA_TRY(check_distinct({d_pos, d_len, d_fsrc}));
     }
     return SA_OK;
 }
@@ -742,7 +733,7 @@ static int lz77_device(sa_context* c, uint64_t n, const uint32_t* d_lpf, const u
                            (const uint16_t*)d_bits, (const int64_t*)d_tcnt, out_cap, d_pos, d_len, d_fsrc);
         SA_HIP(hipGetLastError());
     }
-    uint64_t* h = reinterpret_cast<uint64_t*>(c->host_words + kLzHostWord);
+    uint64_t* h = host_u64<kHwLz, 1>(c);
     SA_HIP(hipMemcpyAsync(h, d_tcnt + (tiles - 1), 8, hipMemcpyDeviceToHost, s));
     SA_HIP(host_sync(s));
     *z = h[0];
@@ -812,10 +803,8 @@ static int lz77_host(const uint8_t* text, uint64_t n, const void* sa, int sa_wid
     if (!z) return set_err(SA_E_INVALID, "z is NULL");
     const int given = (pos_out ? 1 : 0) + (len_out ? 1 : 0) + (src_out ? 1 : 0);
     if (given != 0 && given != 3) return set_err(SA_E_INVALID, "pos_out, len_out and src_out: all or none");
-    if (given && (pos_out == len_out || pos_out == src_out || len_out == src_out))
-        return set_err(SA_E_INVALID, "two outputs are one buffer");
-    for (const void* o : {(const void*)pos_out, (const void*)len_out, (const void*)src_out})
-        if (o && (o == (const void*)text || o == sa)) return set_err(SA_E_INVALID, "an output aliases an input");
+    SA_TRY(check_distinct({pos_out, len_out, src_out}));
+    SA_TRY(check_no_alias({pos_out, len_out, src_out}, {text, sa}));
     *z = 0;
     if (n == 0) return SA_OK;
     std::vector<uint32_t> narrow;

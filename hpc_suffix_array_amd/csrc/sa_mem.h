@@ -51,8 +51,8 @@
 // The seed rule, the left check, the extension and the clamp compile on the
 // host: tests/cpp/mem_check.cpp checks them against brute force.
 // Measurements and the resource report: DESIGN.md section 14.
-// The HIP part needs sa_match.h, sa_locate.h and sa_build.hip's scan_i64
-// before it.
+// The HIP part needs sa_match.h, sa_locate.h and sa_query.h (the candidate
+// tiles, CandList) before it.
 #pragma once
 #include <stdint.h>
 
@@ -135,148 +135,19 @@ static_assert(SA_MEM_INFO == 3 && SA_MEM_TOO_MANY == 1 && SA_MEM_LANE == 1u && S
               "sa_hip.h states these");
 static_assert(kMemLaneBytes % 8 == 0, "whole words");
 
-constexpr int kMemPer = 8;                               // candidates per lane
-constexpr uint32_t kMemTile = kMemPer * kBlock;          // candidates per tile
-constexpr uint32_t kMemGridPerCu = 4;                    // workgroups per CU of the persistent grids
-constexpr int kMemHostWord = 3080;                       // host_words: candidates, skipped | total (8 bytes each)
-static_assert(kMemTile == 2048, "16-bit slots, one flag byte per lane");
-
-// exclusive prefix of v over the workgroup's lanes, and the workgroup's sum
-__device__ __forceinline__ uint32_t mem_block_excl(uint32_t v, uint32_t* s_w, uint32_t& total) {
-    const uint32_t lane = lane_id(), wave = threadIdx.x / kWave;
-    uint32_t incl = v;
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-        const uint32_t y = (uint32_t)__shfl_up((int)incl, o, kWave);
-        if ((int)lane >= o) incl += y;
-    }
-    if (lane == kWave - 1) s_w[wave] = incl;
-    __syncthreads();
-    uint32_t c = 0;
-    total = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < (uint32_t)kWaves; ++w) {
-        const uint32_t x = s_w[w];
-        if (w < wave) c += x;
-        total += x;
-    }
-    __syncthreads();   // s_w may be written again
-    return c + incl - v;
-}
-
-// Tile t of the candidate list: candidates [s, s + cnt); the positions whose
-// list starts inside it are [q_lo, q_hi) (coff(q) in [s, s + cnt)), the empty
-// ones among them included.
-struct MemTile {
-    uint64_t s, q_lo, q_hi;
-    uint32_t cnt;
-};
-
-// The query position of each of the tile's candidates: s_pos[slot] for all
-// kMemTile slots (what lies past cnt repeats the last position), and the
-// calling lane's own kMemPer contiguous slots in pos.  s_q: 2 words, s_w:
-// kWaves words.  Ends with a barrier.
-__device__ __forceinline__ MemTile mem_tile_positions(const uint64_t* __restrict__ coff, uint64_t m, uint64_t t,
-                                                      uint64_t total, uint32_t* s_pos, uint32_t* s_w, uint64_t* s_q,
-                                                      uint32_t (&pos)[kMemPer]) {
-    const uint32_t tid = threadIdx.x, lane = lane_id(), wave = tid / kWave;
-    MemTile r;
-    r.s = t * kMemTile;
-    r.cnt = (uint32_t)std::min<uint64_t>(kMemTile, total - r.s);
-    if (tid == 0) {
-        // coff has m + 1 entries and coff[m] = total >= s + cnt: both bounds are at most m
-        const uint64_t a = locate_lower_bound(LocOff{coff}, 0, m + 1, r.s);
-        s_q[0] = a;
-        s_q[1] = locate_lower_bound(LocOff{coff}, a, m + 1, r.s + r.cnt);
-    }
-    {
-        uint4* mine = reinterpret_cast<uint4*>(s_pos + kMemPer * tid);
-        mine[0] = make_uint4(0u, 0u, 0u, 0u);
-        mine[1] = make_uint4(0u, 0u, 0u, 0u);
-    }
-    __syncthreads();
-    r.q_lo = s_q[0];
-    r.q_hi = s_q[1];
-    // a non-empty position marks the slot of its first candidate with q + 1
-    for (uint64_t q = r.q_lo + tid; q < r.q_hi; q += kBlock) {   // q < m
-        const uint64_t a = coff[q], b = coff[q + 1];
-        if (b > a && a >= r.s && a - r.s < r.cnt) s_pos[a - r.s] = (uint32_t)q + 1u;
-    }
-    __syncthreads();
-    // the position of a slot: the last mark at or below it (marks grow with the
-    // slot); in front of the first mark the position before q_lo, whose list
-    // began in an earlier tile
-    uint32_t mk[kMemPer];
-    {
-        const uint4* mine = reinterpret_cast<const uint4*>(s_pos + kMemPer * tid);
-        const uint4 v0 = mine[0], v1 = mine[1];
-        mk[0] = v0.x; mk[1] = v0.y; mk[2] = v0.z; mk[3] = v0.w;
-        mk[4] = v1.x; mk[5] = v1.y; mk[6] = v1.z; mk[7] = v1.w;
-    }
-    uint32_t last = 0;
-#pragma unroll
-    for (int j = 0; j < kMemPer; ++j) last = std::max(last, mk[j]);
-    uint32_t incl = last;
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-        const uint32_t y = (uint32_t)__shfl_up((int)incl, o, kWave);
-        if ((int)lane >= o) incl = std::max(incl, y);
-    }
-    if (lane == kWave - 1) s_w[wave] = incl;
-    __syncthreads();
-    uint32_t cur = (uint32_t)__shfl_up((int)incl, 1, kWave);
-    if (lane == 0) cur = 0u;
-    for (uint32_t w = 0; w < wave; ++w) cur = std::max(cur, s_w[w]);
-    cur = std::max(cur, (uint32_t)r.q_lo);   // (q_lo - 1) + 1; slot 0 is marked when q_lo == 0
-#pragma unroll
-    for (int j = 0; j < kMemPer; ++j) {
-        cur = std::max(cur, mk[j]);
-        pos[j] = cur ? cur - 1u : 0u;
-    }
-    {
-        uint4* mine = reinterpret_cast<uint4*>(s_pos + kMemPer * tid);
-        mine[0] = make_uint4(pos[0], pos[1], pos[2], pos[3]);
-        mine[1] = make_uint4(pos[4], pos[5], pos[6], pos[7]);
-    }
-    __syncthreads();
-    return r;
-}
-
 __global__ __launch_bounds__(kBlock) void k_mem_seeds(const uint32_t* __restrict__ len, const uint32_t* __restrict__ lo,
                                                       uint32_t* __restrict__ hi, uint64_t m, uint64_t n, uint64_t L,
                                                       uint64_t max_occ, unsigned long long* __restrict__ words) {
-    unsigned long long cand = 0, skip = 0;
+    unsigned long long v[2] = {0, 0};   // candidates, skipped
     for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < m; i += (uint64_t)gridDim.x * kBlock) {
         const uint32_t a = lo[i];
         bool skipped;
         const uint32_t c = mem_seed_count(len[i], a, hi[i], n, L, max_occ, skipped);
         if (c == 0u) hi[i] = a;
-        cand += c;
-        skip += skipped ? 1u : 0u;
+        v[0] += c;
+        v[1] += skipped ? 1u : 0u;
     }
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) {
-        cand += __shfl_down(cand, o, kWave);
-        skip += __shfl_down(skip, o, kWave);
-    }
-    // one pair of atomics per workgroup: every wavefront adding to the same two
-    // words (8192 of them for a 1 MiB query) cost 0.1 ms
-    __shared__ unsigned long long s_c[kWaves], s_s[kWaves];
-    if (lane_id() == 0) {
-        s_c[threadIdx.x / kWave] = cand;
-        s_s[threadIdx.x / kWave] = skip;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        cand = skip = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) {
-            cand += s_c[w];
-            skip += s_s[w];
-        }
-        if (cand) atomicAdd(&words[0], cand);
-        if (skip) atomicAdd(&words[1], skip);
-    }
+    block_sum_u64(v, words);
 }
 
 // flagb[t * kBlock + lane of the workgroup]: bit j = candidate t * kMemTile +
@@ -425,6 +296,12 @@ __global__ __launch_bounds__(kBlock) void k_mem_emit(const uint8_t* __restrict__
     }
 }
 
+static int mem_check_values(uint64_t min_len, uint32_t flags) {
+    if (min_len == 0) return set_err(SA_E_INVALID, "min_len is 0");
+    SA_TRY(check_flags(flags, SA_MEM_LANE | SA_MEM_WAVE));
+    return check_exclusive(flags, SA_MEM_LANE, SA_MEM_WAVE, "SA_MEM_LANE", "SA_MEM_WAVE");
+}
+
 // the checks of sa_mems_device, all before any HIP call
 static int mem_check_args(const sa_context* c, const uint8_t* d_text, uint64_t n, const uint32_t* d_sa,
                           const uint8_t* d_query, uint64_t m, uint64_t min_len, uint32_t flags, const uint64_t* d_off,
@@ -437,20 +314,10 @@ static int mem_check_args(const sa_context* c, const uint8_t* d_text, uint64_t n
     if (n && !d_text) return set_err(SA_E_INVALID, "d_text is NULL");
     if (n && !d_sa) return set_err(SA_E_INVALID, "d_sa is NULL");
     if (m && !d_query) return set_err(SA_E_INVALID, "d_query is NULL");
-    if (min_len == 0) return set_err(SA_E_INVALID, "min_len is 0");
-    if (flags & ~(uint32_t)(SA_MEM_LANE | SA_MEM_WAVE)) return set_err(SA_E_INVALID, "unknown flags %#x", flags);
-    if (flags == (SA_MEM_LANE | SA_MEM_WAVE))
-        return set_err(SA_E_INVALID, "SA_MEM_LANE and SA_MEM_WAVE exclude each other");
+    SA_TRY(mem_check_values(min_len, flags));
     if (!d_tpos != !d_len) return set_err(SA_E_INVALID, "d_tpos and d_len: both or neither");
-    const void* in[3] = {d_text, d_sa, d_query};
-    const void* out[3] = {d_off, d_tpos, d_len};
-    for (const void* o : out)
-        for (const void* i : in)
-            if (o && o == i) return set_err(SA_E_INVALID, "an output aliases an input");
-    if (d_tpos && ((const void*)d_tpos == (const void*)d_len || (const void*)d_tpos == (const void*)d_off ||
-                   (const void*)d_len == (const void*)d_off))
-        return set_err(SA_E_INVALID, "two outputs are one buffer");
-    return SA_OK;
+    SA_TRY(check_no_alias({d_off, d_tpos, d_len}, {d_text, d_sa, d_query}));
+    return check_distinct({d_off, d_tpos, d_len});
 }
 
 // the host form's outputs, allocated when the total is known
@@ -469,17 +336,10 @@ static int mems_device(sa_context* c, const uint8_t* d_text, uint64_t n, const u
     SA_TRY(mem_check_args(c, d_text, n, d_sa, d_query, m, min_len, flags, d_off, d_tpos, d_len, info));
     info[0] = info[1] = info[2] = 0;
     SA_HIP(hipSetDevice(c->device));
-    auto no_mems = [&]() -> int {
-        SA_HIP(hipMemsetAsync(d_off, 0, (m + 1) * 8, s));
-        SA_HIP(host_sync(s));
-        return SA_OK;
-    };
-    if (n == 0 || m == 0 || min_len > std::min(n, m)) return no_mems();
-    uint64_t* h = reinterpret_cast<uint64_t*>(c->host_words + kMemHostWord);
+    if (n == 0 || m == 0 || min_len > std::min(n, m)) return empty_csr(d_off, m, s);
+    uint64_t* h = host_u64<kHwMem, 3>(c);
     const uint32_t sgrid = (uint32_t)std::min<uint64_t>((m + kBlock - 1) / kBlock, (uint64_t)c->cus * 4);
-    uint64_t cands = 0;
-    LocBuf list;   // coff (m + 1) | tile counts | candidates | flag bytes
-    uint64_t* d_coff = nullptr;
+    CandList list;
     {
         LocBuf seeds;   // candidates, skipped | len | lo | hi
         SA_TRY(seeds.alloc(16 + 3 * m * 4, s));
@@ -494,47 +354,28 @@ static int mems_device(sa_context* c, const uint8_t* d_text, uint64_t n, const u
         SA_HIP(hipGetLastError());
         SA_HIP(hipMemcpyAsync(h, d_words, 16, hipMemcpyDeviceToHost, s));
         SA_HIP(host_sync(s));
-        cands = h[0];
-        info[1] = cands;
+        info[1] = h[0];
         info[2] = h[1];
-        SA_TRACE("mems: m %llu candidates %llu skipped %llu", (unsigned long long)m, (unsigned long long)cands,
+        SA_TRACE("mems: m %llu candidates %llu skipped %llu", (unsigned long long)m, (unsigned long long)h[0],
                  (unsigned long long)h[1]);
-        if (max_candidates && cands > max_candidates) {
-            SA_TRY(no_mems());
-            return SA_MEM_TOO_MANY;
-        }
-        if (cands == 0) return no_mems();
-        const uint64_t tiles = (cands + kMemTile - 1) / kMemTile;
-        SA_TRY(list.alloc((m + 1) * 8 + tiles * 8 + align_up(cands, 4) * 4 + tiles * kBlock, s));
-        d_coff = (uint64_t*)list.p;
-        uint32_t* d_cand = (uint32_t*)(d_coff + m + 1 + tiles);
-        uint64_t got = 0;
-        SA_TRY(locate_device(c, n, d_sa, d_lo, d_hi, m, 0, 0, d_coff, d_cand, cands, &got, s));
-        if (got != cands)
-            return set_err(SA_E_INTERNAL, "mems: locate wrote %llu hits for %llu candidates", (unsigned long long)got,
-                           (unsigned long long)cands);
+        const int rc = list.fill(c, "mems", n, d_sa, d_lo, d_hi, m, h[0], max_candidates, SA_MEM_TOO_MANY, d_off, m,
+                                 0, 0, s);
+        if (rc || !list.tiles) return rc;
     }
-    const uint64_t tiles = (cands + kMemTile - 1) / kMemTile;
-    int64_t* d_tcnt = (int64_t*)(d_coff + m + 1);
-    const uint32_t* d_cand = (const uint32_t*)(d_tcnt + tiles);
-    uint8_t* d_flagb = (uint8_t*)(d_cand + align_up(cands, 4));
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(tiles, (uint64_t)c->cus * kMemGridPerCu);
-    hipLaunchKernelGGL(k_mem_flag, dim3(grid), dim3(kBlock), 0, s, d_text, n, d_query, m, (const uint64_t*)d_coff, d_cand,
-                       cands, d_flagb, d_tcnt);
+    hipLaunchKernelGGL(k_mem_flag, dim3(list.grid), dim3(kBlock), 0, s, d_text, n, d_query, m, (const uint64_t*)list.coff,
+                       (const uint32_t*)list.cand, list.cands, list.flagb, list.tcnt);
     SA_HIP(hipGetLastError());
-    SA_TRY(scan_i64<ScanSum>(d_tcnt, tiles, s));
+    SA_TRY(list.scan(s));
     const uint64_t lane_words = flags & SA_MEM_LANE ? ~0ull : flags & SA_MEM_WAVE ? 0ull : kMemLaneBytes / 8;
     auto emit = [&](uint32_t* tp, uint32_t* ln, uint64_t cap) -> int {
-        hipLaunchKernelGGL(k_mem_emit, dim3(grid), dim3(kBlock), 0, s, d_text, n, d_query, m, min_len,
-                           (const uint64_t*)d_coff, d_cand, cands, (const uint8_t*)d_flagb, (const int64_t*)d_tcnt,
-                           lane_words, d_off, tp, ln, cap);
+        hipLaunchKernelGGL(k_mem_emit, dim3(list.grid), dim3(kBlock), 0, s, d_text, n, d_query, m, min_len,
+                           (const uint64_t*)list.coff, (const uint32_t*)list.cand, list.cands,
+                           (const uint8_t*)list.flagb, (const int64_t*)list.tcnt, lane_words, d_off, tp, ln, cap);
         SA_HIP(hipGetLastError());
         return SA_OK;
     };
     if (!own) SA_TRY(emit(d_tpos, d_len, out_cap));
-    SA_HIP(hipMemcpyAsync(h + 2, d_tcnt + (tiles - 1), 8, hipMemcpyDeviceToHost, s));
-    SA_HIP(host_sync(s));
-    info[0] = h[2];
+    SA_TRY(list.total(h + 2, s, &info[0]));
     if (own) {
         const bool fits = own->want && info[0] > 0 && info[0] <= out_cap;
         if (fits) {
@@ -560,16 +401,9 @@ static int mems_host(const uint8_t* text, uint64_t n, const void* sa, int sa_wid
     if (n && !text) return set_err(SA_E_INVALID, "text is NULL");
     if (n && !sa) return set_err(SA_E_INVALID, "sa is NULL");
     if (m && !query) return set_err(SA_E_INVALID, "query is NULL");
-    if (min_len == 0) return set_err(SA_E_INVALID, "min_len is 0");
-    if (flags & ~(uint32_t)(SA_MEM_LANE | SA_MEM_WAVE)) return set_err(SA_E_INVALID, "unknown flags %#x", flags);
-    if (flags == (SA_MEM_LANE | SA_MEM_WAVE))
-        return set_err(SA_E_INVALID, "SA_MEM_LANE and SA_MEM_WAVE exclude each other");
+    SA_TRY(mem_check_values(min_len, flags));
     if (!tpos_out != !len_out) return set_err(SA_E_INVALID, "tpos_out and len_out: both or neither");
-    const void* in[3] = {text, sa, query};
-    const void* out[3] = {off_out, tpos_out, len_out};
-    for (const void* o : out)
-        for (const void* i : in)
-            if (o && o == i) return set_err(SA_E_INVALID, "an output aliases an input");
+    SA_TRY(check_no_alias({off_out, tpos_out, len_out}, {text, sa, query}));
     info[0] = info[1] = info[2] = 0;
     if (n == 0 || m == 0 || min_len > std::min(n, m)) {
         std::memset(off_out, 0, (m + 1) * 8);

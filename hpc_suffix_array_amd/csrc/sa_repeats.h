@@ -62,7 +62,7 @@
 // The walks, the break rank and the supermaximal scan compile on the host:
 // tests/cpp/repeats_check.cpp checks them against the substring dictionary.
 // Measurements and the resource report: DESIGN.md section 16.  The HIP part
-// needs sa_host.h, sa_locate.h (LocBuf), sa_mem.h (mem_block_excl), sa_lz.h
+// needs sa_host.h, sa_locate.h (LocBuf), sa_query.h (mem_block_excl), sa_lz.h
 // and sa_build.hip's scan_i64 and lcp_device before it.
 #pragma once
 #include <stdint.h>
@@ -292,7 +292,6 @@ static_assert(SA_REP_RIGHT == kRepRight && SA_REP_MAXIMAL == kRepMaximal && SA_R
                   SA_REP_INFO == kRepInfo,
               "sa_hip.h states these");
 constexpr uint32_t kRepTileWords = kLzTile / kRepWordRanks;   // 64 words of break bits per tile
-constexpr int kRepHostWord = 3096;                            // host_words: the count, the sum of hi - lo (8 bytes each)
 static_assert(kRepWordRanks == (uint32_t)kWave && kRepTileWords == (uint32_t)kWave,
               "a ballot is a word; one wavefront scans a tile's words");
 
@@ -563,12 +562,8 @@ static int repeats_check_args(const sa_context* c, const uint8_t* d_text, uint64
     if (given) {
         if (((uintptr_t)d_len | (uintptr_t)d_lo | (uintptr_t)d_hi) & 3u)
             return set_err(SA_E_INVALID, "an output is not 4-byte aligned");
-        const void* in[3] = {d_text, d_sa, d_lcp};
-        const void* out[3] = {d_len, d_lo, d_hi};
-        for (const void* i : in)
-            for (const void* o : out)
-                if (i && i == o) return set_err(SA_E_INVALID, "an output aliases an input");
-        if (d_len == d_lo || d_len == d_hi || d_lo == d_hi) return set_err(SA_E_INVALID, "two outputs are one buffer");
+        SA_TRY(check_no_alias({d_len, d_lo, d_hi}, {d_text, d_sa, d_lcp}));
+        SA_TRY(check_distinct({d_len, d_lo, d_hi}));
     }
     return SA_OK;
 }
@@ -652,7 +647,7 @@ static int repeats_device(sa_context* c, const uint8_t* d_text, uint64_t n, cons
                            (const int64_t*)d_tcnt, out_cap, d_len, d_lo, d_hi);
         SA_HIP(hipGetLastError());
     }
-    uint64_t* h = reinterpret_cast<uint64_t*>(c->host_words + kRepHostWord);
+    uint64_t* h = host_u64<kHwRepeats, 2>(c);
     SA_HIP(hipMemcpyAsync(h, d_tcnt + (tiles - 1), 8, hipMemcpyDeviceToHost, s));
     SA_HIP(hipMemcpyAsync(h + 1, d_tocc + (tiles - 1), 8, hipMemcpyDeviceToHost, s));
     SA_HIP(host_sync(s));
@@ -673,10 +668,8 @@ static int repeats_host(const uint8_t* text, uint64_t n, const void* sa, int sa_
     if (n && !sa) return set_err(SA_E_INVALID, "sa is NULL");
     const int given = (len_out ? 1 : 0) + (lo_out ? 1 : 0) + (hi_out ? 1 : 0);
     if (given != 0 && given != 3) return set_err(SA_E_INVALID, "len_out, lo_out and hi_out: all or none");
-    if (given && (len_out == lo_out || len_out == hi_out || lo_out == hi_out))
-        return set_err(SA_E_INVALID, "two outputs are one buffer");
-    for (const void* o : {(const void*)len_out, (const void*)lo_out, (const void*)hi_out})
-        if (o && n && (o == (const void*)text || o == sa)) return set_err(SA_E_INVALID, "an output aliases an input");
+    SA_TRY(check_distinct({len_out, lo_out, hi_out}));
+    if (n) SA_TRY(check_no_alias({len_out, lo_out, hi_out}, {text, sa}));
     std::vector<uint32_t> narrow;
     const void* src32 = nullptr;
     SA_TRY(narrow_sa(sa, n, sa_width, narrow, &src32));

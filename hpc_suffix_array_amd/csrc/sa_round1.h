@@ -363,11 +363,11 @@ static int round1_bucketed(sa_context* c, const uint8_t* d_text, uint64_t n, uin
 #define SA_HIST_G(G, P, L, W)                                                                                 \
     hipLaunchKernelGGL((k_bucket_hist<P, false, L>), dim3(G), dim3(kBlock), 0, s, d_text, n,                  \
                        (const uint16_t*)c->code, bp.bs, os_ghist(c), 0ull, n, blo, bhi, lkeys, lpos, W, rcap,  \
-                       c->words + 11)
+                       c->words + kPadOverWord)
 #define SA_HIST_ID_G(G, L, W)                                                                                 \
     hipLaunchKernelGGL((k_bucket_hist<true, false, L, true>), dim3(G), dim3(kBlock), 0, s, d_text, n,         \
                        (const uint16_t*)c->code, bp.bs, os_ghist(c), 0ull, n, blo, bhi, lkeys, lpos, W, rcap,  \
-                       c->words + 11)
+                       c->words + kPadOverWord)
 #define SA_HIST(P, L, W) SA_HIST_G(g, P, L, W)
 #define SA_HIST_ID(L, W) SA_HIST_ID_G(g, L, W)
         const bool ident = bp.bs.sigma == 256;
@@ -380,13 +380,13 @@ static int round1_bucketed(sa_context* c, const uint8_t* d_text, uint64_t n, uin
             else if (pow2 && SA_DNA_SWAR && c->dna)
                 hipLaunchKernelGGL((k_bucket_hist<true, false, 3, false, true>), dim3(rgrid), dim3(kBlock), 0, s, d_text,
                                    n, (const uint16_t*)c->code, bp.bs, os_ghist(c), 0ull, n, blo, bhi, lkeys, lpos, rcur,
-                                   rcap, c->words + 11);
+                                   rcap, c->words + kPadOverWord);
             else if (pow2) SA_HIST_G(rgrid, true, 3, rcur);
             else SA_HIST_G(rgrid, false, 3, rcur);
             // an overflowed stripe dropped records: stop before any pass reads them
-            SA_HIP(hipMemcpyAsync(c->host_words + 11, c->words + 11, 4, hipMemcpyDeviceToHost, s));
+            SA_HIP(hipMemcpyAsync(c->host_words + kPadOverWord, c->words + kPadOverWord, 4, hipMemcpyDeviceToHost, s));
             SA_HIP(host_sync(s));
-            if (c->host_words[11]) {
+            if (c->host_words[kPadOverWord]) {
                 SA_TRACE("  bucketed round 1: a record stripe overflowed, again with the counting scan");
                 tm.end();
                 const int rc = round1_bucketed(c, d_text, n, d_sa, bp, br_, s, tm, st, done, fused, seg, ksh, false,
@@ -521,7 +521,7 @@ static int round1_bucketed(sa_context* c, const uint8_t* d_text, uint64_t n, uin
     hipLaunchKernelGGL((k_split_text<kItemsA, BLK, P, PK, DNA, ID>), dim3(text_grid(BLK)), dim3(BLK), 0, s, d_text, n, \
                        (const uint16_t*)c->code, bp.bs, (const uint32_t*)(padded ? pstart : os_base(c)),           \
                        os_tickets(c), c->keys[0], c->vals_alt, g_hi, cursor, m, blo, bhi,                          \
-                       padded ? (const uint32_t*)pstart + 1 : nullptr, padded ? c->words + 11 : nullptr, hb, bp.ib, \
+                       padded ? (const uint32_t*)pstart + 1 : nullptr, padded ? c->words + kPadOverWord : nullptr, hb, bp.ib, \
                        stripes, alpha_bad)
         if (listed) {
             constexpr int kItemsL = SA_ITEMS_B, kListBlock = SA_LIST_BLOCK;
@@ -544,7 +544,7 @@ static int round1_bucketed(sa_context* c, const uint8_t* d_text, uint64_t n, uin
                        dim3(kSpBlock), 0, s, d_text, n, (const uint16_t*)c->code, bp.bs,                           \
                        (const uint32_t*)(padded ? pstart : os_base(c)), os_tickets(c), c->keys[0], c->vals_alt, g_hi, \
                        cursor, m, blo, bhi, padded ? (const uint32_t*)pstart + 1 : nullptr,                        \
-                       padded ? c->words + 11 : nullptr, hb, bp.ib, stripes, alpha_bad)
+                       padded ? c->words + kPadOverWord : nullptr, hb, bp.ib, stripes, alpha_bad)
             if (bp.bs.powR1 * (uint64_t)bp.bs.sigma <= 0xFFFFFFFFull && !(((uint32_t)c->tune >> 28) & 1u))
                 SA_TEXT_NP2(true);
             else
@@ -566,7 +566,7 @@ static int round1_bucketed(sa_context* c, const uint8_t* d_text, uint64_t n, uin
                                dim3(text_grid(kSpBlock)), dim3(kSpBlock), 0, s, d_text, n, (const uint16_t*)c->code,
                                bp.bs, (const uint32_t*)(padded ? pstart : os_base(c)), os_tickets(c), c->keys[0],
                                c->vals_alt, g_hi, cursor, m, blo, bhi, padded ? (const uint32_t*)pstart + 1 : nullptr,
-                               padded ? c->words + 11 : nullptr, hb, bp.ib, stripes, alpha_bad);
+                               padded ? c->words + kPadOverWord : nullptr, hb, bp.ib, stripes, alpha_bad);
         } else {
             SA_TEXT_PASS(false, false, kSpBlock, false, false);
         }
@@ -704,7 +704,7 @@ static int round1_bucketed(sa_context* c, const uint8_t* d_text, uint64_t n, uin
         return SA_OK;
     }
     if (c->host_words[4]) return set_err(SA_E_INTERNAL, "radix look-back did not complete");
-    if (padded && c->host_words[11]) {   // a digit outgrew its sampled segment: exact totals
+    if (padded && c->host_words[kPadOverWord]) {   // a digit outgrew its sampled segment: exact totals
         SA_TRACE("  bucketed round 1: padded segment overflow, again with exact digit totals");
         const int rc = round1_bucketed(c, d_text, n, d_sa, bp, br_, s, tm, st, done, fused, seg, ksh, false, allow_xq,
                                        round2);

@@ -23,5 +23,19 @@ int main() {
     bad += xq_offsets_fit(0xFFFFFFFFull);
     bad += !(mmax > 3900000000ull && mmax < 4100000000ull);
     std::printf("xq max m %llu bad %d\n", (unsigned long long)mmax, bad);
+    // the map of the pinned words, as sa_limits.h's static_asserts state it:
+    // every region inside the block, no two sharing a word, a region read as
+    // 64-bit words made of whole ones
+    for (int i = 0; i < kHwCount; ++i) {
+        const HostRegion a = kHostRegions[i];
+        bad += !(a.len > 0 && a.at + a.len <= kHostWords);
+        bad += a.wide && (a.at % 2 || a.len % 2);
+        for (int j = 0; j < i; ++j) {
+            const HostRegion b = kHostRegions[j];
+            bad += a.at < b.at + b.len && b.at < a.at + a.len;
+        }
+    }
+    bad += !(hw(kHwHamming).len == 4 && hw(kHwWords).at == 0);   // the rows follow HwId
+    std::printf("host regions %d bad %d\n", (int)kHwCount, bad);
     return bad ? 1 : 0;
 }

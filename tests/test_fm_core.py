@@ -100,7 +100,13 @@ def test_host_waits_stated_and_counted():
     b = body("fm_build_device")
     assert b.index("host_sync(") < b.index("k_fm_records") < b.index("k_fm_samples")
     b = body("fm_locate_device")
-    assert b.count("host_sync(") == 2 and b.index("host_sync(") < b.index("k_fm_resolve") < b.index("locate_device_n(")
+    assert b.count("host_sync(") == 2 and b.index("host_sync(") < b.index("k_fm_resolve") < b.index("tmp.sort(")
+    # the sort is sa_query.h's step: it adds no wait of its own in front of sa_locate_device's
+    q = open(os.path.join(CSRC, "sa_query.h")).read()
+    for start, end in (("static int sort_lists(", "\n}\n"), ("struct ListSort {", "\n};\n")):
+        step = q[q.index(start):q.index(end, q.index(start))]
+        assert "host_sync(" not in step and "hipMemcpy" not in step
+    assert step.index("k_list_ranges") < step.index("sort_lists(") and "locate_device_n(" in q[q.index("static int sort_lists("):]
 
 
 def test_symbols_exported_and_listed(sa_lib):
