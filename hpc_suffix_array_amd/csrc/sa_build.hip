@@ -24,6 +24,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/sa_hip.h"
@@ -115,7 +116,7 @@ static_assert(kMaxChunks >= 1 && kMaxChunks <= (1u << 20), "chunk scratch sized 
 // sparse round-1 ranks when at most n / kSparseDiv suffixes stay unsorted
 constexpr uint64_t kSparseDiv = 8;
 constexpr int kEvPool = 256;
-constexpr int kRoundEv = SA_MAX_ROUNDS + 1;   // round boundary events (Timer::round_mark)
+constexpr int kRoundEv = SA_MAX_ROUNDS + 1;   // round boundary events (Run::round_mark)
 constexpr int kSyncEv = kEvPool + kRoundEv;   // recorded behind a read-back the host waits for (host_sync_event)
 
 static uint64_t align_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
@@ -176,7 +177,7 @@ struct sa_context {
     uint32_t* alpha = nullptr;     // 256 byte counts
     uint16_t* code = nullptr;      // 256 byte -> dense code 1..sigma
     uint32_t* host_words = nullptr;  // pinned, sa::kHostWords words: the regions are sa_limits.h's table (kHw*)
-    hipEvent_t ev[sa::kEvPool + sa::kRoundEv + 1];   // Timer pairs, the round boundaries, a read-back (kSyncEv)
+    hipEvent_t ev[sa::kEvPool + sa::kRoundEv + 1];   // Run timing pairs, the round boundaries, a read-back (kSyncEv)
     int ev_ready = 0;
     sa::DistState* dist = nullptr;   // range-partitioned build state (sa_dist.h)
     // sa_opts debug / tune fields of the current build (sa_build_device's
@@ -359,12 +360,18 @@ static bool gs_available(sa_context* c, uint64_t n) {
 // set i's group-start buffer when it holds an n-suffix build's groups
 static uint32_t* gs_buf(const sa_context* c, uint64_t n, int i) { return n <= c->gscap ? c->u_gs[i] : nullptr; }
 
-// Per-launch HIP-event timing, enabled by sa_opts.profile.
-struct Timer {
+// One build's run context: the context, stream and statistics every build-side
+// helper works on, with the per-launch HIP-event timing of sa_opts.profile
+// (`on`).  Run{c, s, false, nullptr}: no timing, no statistics.
+struct Run {
     sa_context* c;
     hipStream_t s;
     bool on;
     sa_stats* st;
+    // algorithmic bytes moved by a kind of launch
+    void bytes(int k, uint64_t b) {
+        if (st) st->kern_bytes[k] += b;
+    }
     int used = 0;
     int kind[kEvPool / 2];
     void begin(int k) {
@@ -444,34 +451,30 @@ static float elapsed(hipEvent_t a, hipEvent_t b) {
     return ms;
 }
 
-static void add_bytes(sa_stats* st, int kind, uint64_t b) {
-    if (st) st->kern_bytes[kind] += b;
+// The read-back of a few words: `bytes` from d_src into the pinned words at
+// `at`, and the host waits for them.  Returns them, or nullptr (the error set).
+static const uint32_t* read_back(sa_context* c, uint32_t at, const void* d_src, size_t bytes, hipStream_t s) {
+    uint32_t* const h = c->host_words + at;
+    hipError_t e = hipMemcpyAsync(h, d_src, bytes, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = host_sync(s);
+    if (e == hipSuccess) return h;
+    set_err(SA_E_HIP, "read-back of %zu bytes failed: %s", bytes, hipGetErrorString(e));
+    return nullptr;
 }
+// the first `bytes` of words[], or words[k] alone, into their mirror (kHwWords; indexed by the k*Word names)
+static const uint32_t* read_words(sa_context* c, size_t bytes, hipStream_t s) { return read_back(c, 0, c->words, bytes, s); }
+static const uint32_t* read_word(sa_context* c, int k, hipStream_t s) { return read_back(c, k, c->words + k, 4, s); }
+#define SA_READ(var, ...)                         \
+    const uint32_t* const var = (__VA_ARGS__);    \
+    if (!var) return SA_E_HIP
 
-// One LSD radix pass over bits [shift, shift + nbits).
-template <class Src>
-static int radix_pass(sa_context* c, const Src& src, const Chunking& ch, uint32_t shift, uint32_t nbits,
-                      uint64_t* out_keys, uint32_t* out_vals, hipStream_t s, Timer& tm, sa_stats* st,
-                      int kind_hist, int kind_scatter, uint64_t in_bytes, bool hist_ready = false) {
-    const uint32_t mask = (1u << nbits) - 1u;
-    if (!hist_ready) {
-        tm.begin(kind_hist);
-        hipLaunchKernelGGL(k_hist<Src>, dim3(ch.chunks), dim3(kBlock), 0, s, src, ch, shift, mask, c->hist);
-        tm.end();
-        add_bytes(st, kind_hist, in_bytes);
-    }
-    tm.begin(SA_K_SCAN);
-    hipLaunchKernelGGL(k_scan_rows, dim3(kRadix), dim3(kBlock), 0, s, c->hist, ch.chunks, c->totals);
-    tm.end();
-    tm.begin(kind_scatter);
-    hipLaunchKernelGGL(k_scatter<Src>, dim3(ch.chunks), dim3(kBlock), 0, s, src, ch, shift, nbits,
-                       (const uint32_t*)c->hist, (const uint32_t*)c->totals, out_keys, out_vals);
-    tm.end();
-    SA_HIP(hipGetLastError());
-    add_bytes(st, SA_K_SCAN, 2ull * 4 * kRadix * ch.chunks);
-    add_bytes(st, kind_scatter, in_bytes + 12ull * ch.n);
-    return SA_OK;
-}
+// the D, m, G totals of a set of suffixes: distinct keys (group heads), the
+// unsorted suffixes left and their groups
+struct SetTotals {
+    uint64_t D = 0, m = 0, G = 0;
+};
+static SetTotals totals_of(const uint32_t* w) { return SetTotals{w[kDWord], w[kMWord], w[kGWord]}; }
+static SetTotals operator+(const SetTotals& a, const SetTotals& b) { return SetTotals{a.D + b.D, a.m + b.m, a.G + b.G}; }
 
 // single-pass (onesweep) scratch: ghist[8][256] | base[8][256] | tickets[8]
 static uint32_t* os_ghist(sa_context* c) { return c->os; }
@@ -495,97 +498,105 @@ static uint32_t next_epoch(sa_context* c, hipStream_t s) {
     return c->epoch;
 }
 
+// pass p of a sort (its digit bases and ticket in the onesweep scratch)
 template <class Src, int RBITS = 8>
-static void onesweep_pass(sa_context* c, const Src& src, uint64_t n, uint32_t shift, uint32_t nbits,
-                          const uint32_t* base, uint32_t* ticket, uint64_t* out_keys, uint32_t* out_vals,
-                          hipStream_t s) {
+static void onesweep_pass(Run& r, const Src& src, uint64_t n, uint32_t shift, uint32_t nbits, uint32_t p,
+                          uint64_t* out_keys, uint32_t* out_vals) {
+    sa_context* const c = r.c;
     const uint64_t tiles = (n + kTile - 1) / kTile;
-    const uint32_t epoch = next_epoch(c, s);
+    const uint32_t epoch = next_epoch(c, r.s);
     // 1024 x 4: 16 waves per tile, 2 workgroups (32 waves) per CU -- the
     // fastest shape in microbench.hip (r01: 10.4 ms per 2^30-pair pass)
     static_assert(kOsBlock * kOsItems == kTile, "tile states are sized for kTile");
-    hipLaunchKernelGGL((k_onesweep<Src, kOsBlock, kOsItems, RBITS>), dim3((uint32_t)tiles), dim3(kOsBlock), 0, s, src,
-                       n, shift, nbits, base, c->states, ticket, epoch, out_keys, out_vals, c->words + 4);
+    hipLaunchKernelGGL((k_onesweep<Src, kOsBlock, kOsItems, RBITS>), dim3((uint32_t)tiles), dim3(kOsBlock), 0, r.s, src,
+                       n, shift, nbits, (const uint32_t*)(os_base(c) + p * kRadix), c->states, os_tickets(c) + p, epoch,
+                       out_keys, out_vals, c->words + kLookbackWord);
 }
+
+// the buffers of a sort: the sorted idx land in vals_final, the pairs
+// ping-pong through vals_other and the two key buffers
+struct SortBufs {
+    uint32_t *vals_final, *vals_other;
+    uint64_t *kb0, *kb1;
+};
+struct Sorted {
+    uint64_t* keys = nullptr;   // the key buffer that holds the sorted keys
+    uint32_t passes = 0;
+};
+// hist0_ready: the first source's histograms are already computed (per chunk
+// for the reduce-then-scan sort; global, after onesweep_prepare, otherwise).
+// usort: an unsorted-set sort, accounted apart from the full-n passes
+struct SortFlags {
+    bool hist0_ready = false, usort = false;
+};
 
 // Stable LSD sort of ch.n (key, idx) pairs over key bits [0, bits): the first
 // pass generates pairs from `first`, later passes read the ping-pong buffers.
-// The sorted idx land in vals_final; *sorted_keys = the sorted key buffer.
-// hist0_ready: the first source's histograms are already computed (per chunk
-// for the reduce-then-scan sort; global, after onesweep_prepare, otherwise).
 template <class Src>
-static int radix_sort(sa_context* c, const Src& first, uint64_t first_bytes, const Chunking& ch, uint32_t bits,
-                      uint32_t* vals_final, uint32_t* vals_other, uint64_t* kb0, uint64_t* kb1, hipStream_t s,
-                      Timer& tm, sa_stats* st, uint64_t** sorted_keys, uint32_t* passes, bool hist0_ready = false,
-                      bool usort = false) {
+static int radix_sort(Run& r, const Src& first, uint64_t first_bytes, const Chunking& ch, uint32_t bits,
+                      const SortBufs& b, Sorted* out, SortFlags f = SortFlags{}) {
+    sa_context* const c = r.c;
     const uint32_t P = (bits + 7) / 8;
     if (P > kMaxPasses) return set_err(SA_E_INTERNAL, "%u radix passes", P);
-    // an unsorted-set sort (later rounds, few suffixes) is accounted apart so
-    // the per-kind averages of the full-n passes stay per-launch comparable
-    const int k_hist = usort ? SA_K_SORT_U : SA_K_HIST_FIRST;
-    const int k_first = usort ? SA_K_SORT_U : SA_K_SCATTER_FIRST;
-    const int k_keys = usort ? SA_K_SORT_U : SA_K_SCATTER_KEYS;
+    const int k_hist = f.usort ? SA_K_SORT_U : SA_K_HIST_FIRST;
+    uint32_t* vb[2];
+    vb[(P - 1) & 1] = b.vals_final;
+    vb[P & 1] = b.vals_other;
+    uint64_t* kb[2] = {b.kb0, b.kb1};
+    out->keys = kb[(P - 1) & 1];
+    out->passes = P;
     if (c->radix == 0) {
         const uint64_t n = ch.n;
-        uint32_t* vb[2];
-        vb[(P - 1) & 1] = vals_final;
-        vb[P & 1] = vals_other;
-        uint64_t* kb[2] = {kb0, kb1};
-        if (!hist0_ready) {
-            int rc = onesweep_prepare(c, s);
-            if (rc) return rc;
-            tm.begin(k_hist);
+        if (!f.hist0_ready) {
+            SA_TRY(onesweep_prepare(c, r.s));
+            r.begin(k_hist);
             const uint32_t grid = (uint32_t)std::min<uint64_t>((n + kBlock - 1) / kBlock, 2048);
-            hipLaunchKernelGGL(k_global_hist<Src>, dim3(grid), dim3(kBlock), 0, s, first, n, P, os_ghist(c),
+            hipLaunchKernelGGL(k_global_hist<Src>, dim3(grid), dim3(kBlock), 0, r.s, first, n, P, os_ghist(c),
                                bits >= 64 ? ~0ull : (1ull << bits) - 1ull);
-            tm.end();
-            add_bytes(st, k_hist, first_bytes);
+            r.end();
+            r.bytes(k_hist, first_bytes);
         }
-        tm.begin(SA_K_SCAN);
-        hipLaunchKernelGGL(k_digit_base, dim3(P), dim3(kBlock), 0, s, (const uint32_t*)os_ghist(c), os_base(c));
-        tm.end();
-        for (uint32_t p = 0; p < P; ++p) {
-            const uint32_t shift = 8 * p;
-            const uint32_t nbits = std::min<uint32_t>(8, bits - shift);
-            if (p == 0) {
-                tm.begin(k_first);
-                onesweep_pass(c, first, n, shift, nbits, os_base(c), os_tickets(c), kb[0], vb[0], s);
-                tm.end();
-                add_bytes(st, k_first, first_bytes + 12 * n);
-            } else {
-                SrcKeys src{kb[(p - 1) & 1], vb[(p - 1) & 1]};
-                tm.begin(k_keys);
-                onesweep_pass(c, src, n, shift, nbits, os_base(c) + p * kRadix, os_tickets(c) + p, kb[p & 1],
-                              vb[p & 1], s);
-                tm.end();
-                add_bytes(st, k_keys, 24 * n);
-            }
-        }
-        SA_HIP(hipGetLastError());
-        *sorted_keys = kb[(P - 1) & 1];
-        *passes = P;
-        return SA_OK;
+        r.begin(SA_K_SCAN);
+        hipLaunchKernelGGL(k_digit_base, dim3(P), dim3(kBlock), 0, r.s, (const uint32_t*)os_ghist(c), os_base(c));
+        r.end();
     }
-    uint32_t* vb[2];
-    vb[(P - 1) & 1] = vals_final;
-    vb[P & 1] = vals_other;
-    uint64_t* kb[2] = {kb0, kb1};
     for (uint32_t p = 0; p < P; ++p) {
         const uint32_t shift = 8 * p;
         const uint32_t nbits = std::min<uint32_t>(8, bits - shift);
-        int rc;
-        if (p == 0) {
-            rc = radix_pass(c, first, ch, shift, nbits, kb[0], vb[0], s, tm, st, k_hist, k_first, first_bytes,
-                            hist0_ready);
-        } else {
-            SrcKeys src{kb[(p - 1) & 1], vb[(p - 1) & 1]};
-            rc = radix_pass(c, src, ch, shift, nbits, kb[p & 1], vb[p & 1], s, tm, st,
-                            usort ? SA_K_SORT_U : SA_K_HIST_KEYS, k_keys, 12 * ch.n);
-        }
-        if (rc) return rc;
+        const int kh = f.usort || !p ? k_hist : SA_K_HIST_KEYS;
+        const int ks = f.usort ? SA_K_SORT_U : p ? SA_K_SCATTER_KEYS : SA_K_SCATTER_FIRST;
+        const uint64_t in_bytes = p ? 12 * ch.n : first_bytes;
+        auto pass = [&](const auto& src) {
+            using S = std::decay_t<decltype(src)>;
+            if (c->radix == 0) {
+                r.begin(ks);
+                onesweep_pass(r, src, ch.n, shift, nbits, p, kb[p & 1], vb[p & 1]);
+                r.end();
+                r.bytes(ks, in_bytes + 12 * ch.n);
+                return;
+            }
+            // reduce-then-scan: chunk histograms, their scan, the scatter
+            if (p || !f.hist0_ready) {
+                r.begin(kh);
+                hipLaunchKernelGGL(sa::k_hist<S>, dim3(ch.chunks), dim3(kBlock), 0, r.s, src, ch, shift,
+                                   (1u << nbits) - 1u, c->hist);
+                r.end();
+                r.bytes(kh, in_bytes);
+            }
+            r.begin(SA_K_SCAN);
+            hipLaunchKernelGGL(k_scan_rows, dim3(kRadix), dim3(kBlock), 0, r.s, c->hist, ch.chunks, c->totals);
+            r.end();
+            r.begin(ks);
+            hipLaunchKernelGGL(k_scatter<S>, dim3(ch.chunks), dim3(kBlock), 0, r.s, src, ch, shift, nbits,
+                               (const uint32_t*)c->hist, (const uint32_t*)c->totals, kb[p & 1], vb[p & 1]);
+            r.end();
+            r.bytes(SA_K_SCAN, 2ull * 4 * kRadix * ch.chunks);
+            r.bytes(ks, in_bytes + 12ull * ch.n);
+        };
+        if (p == 0) pass(first);
+        else pass(SrcKeys{kb[(p - 1) & 1], vb[(p - 1) & 1]});
     }
-    *sorted_keys = kb[(P - 1) & 1];
-    *passes = P;
+    SA_HIP(hipGetLastError());
     return SA_OK;
 }
 
@@ -615,16 +626,19 @@ static void record_round(sa_stats* st, float ms, uint64_t D, uint32_t P, uint64_
 constexpr int kPermErrWord = 13;
 static uint64_t perm_min_n(const sa_context* c) { return (c->dbg & SA_DEBUG_PERM_ALWAYS) ? 1ull : (1ull << 22); }
 
-static PermPlan plan_perm(uint64_t n) {
+// bin shifts of a permutation with 2^b1 first-level bins and sub-bins of 2^s2
+// (the re-rank's; the checker's and the LCP's passes choose theirs)
+static PermPlan plan_check(uint64_t n, uint32_t s2, uint32_t b1 = 8) {
     PermPlan p;
     const uint32_t lg = bit_width(n > 1 ? n - 1 : 1);   // ceil(log2 n)
-    p.s2 = kPermSub;
-    p.s1 = std::max<uint32_t>(p.s2, lg > 8 ? lg - 8 : 0);
+    p.s2 = s2;
+    p.s1 = std::max<uint32_t>(s2, lg > b1 ? lg - b1 : 0);
     p.nb1 = (uint32_t)((n + (1ull << p.s1) - 1) >> p.s1);
     p.nsub = 1u << (p.s1 - p.s2);
     p.tpb = (uint32_t)(((1ull << p.s1) + kPermBlock * kPermItems - 1) / (kPermBlock * kPermItems));
     return p;
 }
+static PermPlan plan_perm(uint64_t n) { return plan_check(n, kPermSub); }
 
 // rank[idx[p]] = dense rank of sorted position p, through the two key
 // buffers (the sorted keys are read by the first step and then free)
@@ -635,8 +649,10 @@ static uint32_t* perm_tile_off(sa_context* c) { return c->hist + ((uint64_t)kRad
 // tickets of the persistent permutation kernels: below the re-rank's tile offsets in hist
 static uint32_t* perm_tickets(sa_context* c) { return c->hist + ((uint64_t)kRadix * kMaxChunks) / 2 - 64; }
 
-static int rerank_permute(sa_context* c, uint64_t* sorted, const uint32_t* d_sa, const Chunking& ch,
-                          hipStream_t s, Timer& tm, sa_stats* st, uint32_t kshift = 0, NextHist nh = NextHist{}) {
+static int rerank_permute(Run& r, uint64_t* sorted, const uint32_t* d_sa, const Chunking& ch, uint32_t kshift = 0,
+                          NextHist nh = NextHist{}) {
+    sa_context* const c = r.c;
+    const hipStream_t s = r.s;
     const uint64_t n = ch.n;
     const PermPlan p = plan_perm(n);
     const uint64_t half = (uint64_t)kRadix * kMaxChunks / 2;   // cursors below, tile offsets above
@@ -647,7 +663,7 @@ static int rerank_permute(sa_context* c, uint64_t* sorted, const uint32_t* d_sa,
     uint32_t* cur1 = c->hist;          // the chunk histograms are free after the sort
     uint32_t* cur2 = c->hist + 256;
     SA_HIP(hipMemsetAsync(c->hist, 0, (256ull + (uint64_t)p.nb1 * p.nsub) * 4, s));
-    tm.begin(SA_K_RERANK);
+    r.begin(SA_K_RERANK);
     const uint32_t tiles = (uint32_t)((n + kPermTile - 1) / kPermTile);
     const uint32_t* toff = perm_tile_off(c);
     if (kshift)   // packed (key << kshift | idx) items
@@ -681,9 +697,9 @@ static int rerank_permute(sa_context* c, uint64_t* sorted, const uint32_t* d_sa,
         hipLaunchKernelGGL((k_perm_place<kPermBlock>), dim3((uint32_t)((n + (1ull << kPermSub) - 1) >> kPermSub)),
                            dim3(kPermBlock), 0, s, placed, n, c->rank, c->words + kPermErrWord);
     }
-    tm.end();
+    r.end();
     SA_HIP(hipGetLastError());
-    add_bytes(st, SA_K_RERANK, (p.s1 > p.s2 ? 48ull : 32ull) * n - (kshift ? 4ull * n : 0ull));
+    r.bytes(SA_K_RERANK, (p.s1 > p.s2 ? 48ull : 32ull) * n - (kshift ? 4ull * n : 0ull));
     return SA_OK;
 }
 
@@ -738,10 +754,22 @@ static int blocks_per_cu(K kernel, int block) {
 // XQ (sa_lsd.h): per-XCD queues of tiles; base = qbase[8][1024], ticket =
 // the pass's 8 queue tickets, next_hist = the next pass's per-queue counts;
 // the grid is whole XCDs (every queue served)
+// where a pass finds its digit bases and ticket(s) and writes its pairs; the
+// next pass's digit, counted by this one into next_hist (null: the last pass)
+struct LsdIo {
+    const uint32_t* base;
+    uint32_t* ticket;
+    uint64_t* ok;
+    uint32_t* ov;
+    uint32_t nshift, nnbits;
+    uint32_t* next_hist;
+    QDiv qd;
+    uint32_t tpq;
+};
 template <class Src, bool PACKED, bool XQ = false>
-static int lsd_pass(sa_context* c, const Src& src, uint64_t n, uint32_t shift, uint32_t nbits, const uint32_t* base,
-                     uint32_t* ticket, uint64_t* ok, uint32_t* ov, hipStream_t s, uint32_t nshift, uint32_t nnbits,
-                     uint32_t* next_hist, QDiv qd = QDiv{}, uint32_t tpq = 0) {
+static int lsd_pass(Run& r, const Src& src, uint64_t n, uint32_t shift, uint32_t nbits, const LsdIo& io) {
+    sa_context* const c = r.c;
+    const hipStream_t s = r.s;
     const uint32_t epoch = next_epoch(c, s);
     uint64_t tiles = 0;
     unsigned long long* prof = reinterpret_cast<unsigned long long*>(lsd_tickets(c) + kMaxPasses);
@@ -756,8 +784,8 @@ static int lsd_pass(sa_context* c, const Src& src, uint64_t n, uint32_t shift, u
         if (!per_cu.load(std::memory_order_relaxed)) per_cu.store(blocks_per_cu(kern, B));                  \
         const uint64_t grid = (uint64_t)c->cus * (uint64_t)per_cu.load(std::memory_order_relaxed);          \
         hipLaunchKernelGGL(kern, dim3((uint32_t)(XQ ? grid : std::min<uint64_t>(tiles, grid))), dim3(B), 0, s, \
-                           src, n, shift, nbits, base, c->states, ticket, epoch, ok, ov, c->words + 4, prof,   \
-                           nshift, nnbits, next_hist, qd, tpq);                                            \
+                           src, n, shift, nbits, io.base, c->states, io.ticket, epoch, io.ok, io.ov,             \
+                           c->words + kLookbackWord, prof, io.nshift, io.nnbits, io.next_hist, io.qd, io.tpq);   \
     } while (0)
     if (nbits <= 8) SA_LSD_LAUNCH(8);
     else if (nbits == 9) SA_LSD_LAUNCH(9);
@@ -788,22 +816,26 @@ static bool lsd_xq_ok(const sa_context* c, uint64_t n, const LsdPlan& pl, bool p
         for (uint32_t p = 0; p < pl.P; ++p) xq = xq && pl.bits[p] <= 9;
     return xq;
 }
-static void lsd_xq_span(uint64_t n, uint32_t* tpq, uint64_t* qspan, QDiv* qd) {
+// the span of a queue (qspan pairs = tpq tiles) and its divider, in the
+// NextHist the re-rank takes them in
+static NextHist lsd_xq_span(uint64_t n) {
     const uint64_t xtiles = (n + kLsdXqTile - 1) / kLsdXqTile;
-    *tpq = (uint32_t)((xtiles + 7) / 8);
-    *qspan = (uint64_t)*tpq * kLsdXqTile;
-    qd->magic = (uint64_t)((((unsigned __int128)1 << 64) + *qspan - 1) / *qspan);
+    NextHist x;
+    x.qspan = (xtiles + 7) / 8 * kLsdXqTile;
+    x.qd.magic = (uint64_t)((((unsigned __int128)1 << 64) + x.qspan - 1) / x.qspan);
+    return x;
 }
 
 // Stable LSD sort of n pairs by the plan's digits, pass 0 reading `first`.
 // PACKED: one item buffer ping-pong; else keys + values, the last pass
-// writing its values into vals_final.  *sorted = the sorted key / item buffer.
+// writing its values into vals_final.  sorted->keys: the sorted key / item buffer.
 // hist_ready (XQ): the first pass's per-queue counts are already in
 // lsdx[0] (the previous round's k_perm_place counted them).
 template <bool PACKED, class Src0>
-static int lsd_sort(sa_context* c, const Src0& first, uint64_t n, const LsdPlan& pl, uint32_t* vals_final,
-                    uint32_t* vals_other, hipStream_t s, Timer& tm, sa_stats* st, uint64_t** sorted,
-                    bool hist_ready = false) {
+static int lsd_sort(Run& r, const Src0& first, uint64_t n, const LsdPlan& pl, uint32_t* vals_final,
+                    uint32_t* vals_other, Sorted* sorted, bool hist_ready = false) {
+    sa_context* const c = r.c;
+    const hipStream_t s = r.s;
     if (pl.P < 1 || pl.P > kMaxPasses) return set_err(SA_E_INTERNAL, "%u radix passes", pl.P);
     uint64_t* kb[2] = {c->keys[0], c->keys[1]};
     uint32_t* vb[2];
@@ -813,974 +845,68 @@ static int lsd_sort(sa_context* c, const Src0& first, uint64_t n, const LsdPlan&
     // the first digit's totals here; every pass counts the next one's
     LsdPlan first_only = pl;
     first_only.P = 1;
-    // per-XCD queues of tiles (sa_lsd.h XQ)
-    if (lsd_xq_ok(c, n, pl, PACKED)) {
-        uint32_t tpq;
-        uint64_t qspan;
-        QDiv qd;
-        lsd_xq_span(n, &tpq, &qspan, &qd);
-        uint32_t* const qh = c->lsdx;                                    // [pass][8][1024]
-        uint32_t* const qb = qh + kMaxPasses * 8 * kLsdMaxRadix;         // [8][1024]
-        uint32_t* const qt = qb + 8 * kLsdMaxRadix;                      // [pass][8 x 32]
-        if (hist_ready) {   // pass 0's counts came with the previous round's re-rank
-            SA_HIP(hipMemsetAsync(c->lsdx + 8 * kLsdMaxRadix, 0, (kLsdXqWords - 8 * kLsdMaxRadix) * 4, s));
-        } else {
-            SA_HIP(hipMemsetAsync(c->lsdx, 0, kLsdXqWords * 4, s));
-            tm.begin(SA_K_HIST_FIRST);
-            hipLaunchKernelGGL(k_lsd_hist<Src0>, dim3((uint32_t)std::min<uint64_t>((n + 8 * kBlock - 1) / (8 * kBlock),
-                                                                                   (uint64_t)c->cus * 4)),
-                               dim3(kBlock), 0, s, first, n, first_only, qh, qd);
-            tm.end();
-            add_bytes(st, SA_K_HIST_FIRST, 8 * n);
-        }
-        const uint64_t pair = PACKED ? 8 : 12;
-        for (uint32_t p = 0; p < pl.P; ++p) {
-            tm.begin(SA_K_SCAN);
+    const uint64_t pair = PACKED ? 8 : 12;
+    const dim3 hgrid((uint32_t)std::min<uint64_t>((n + 8 * kBlock - 1) / (8 * kBlock), (uint64_t)c->cus * 4));
+    // pass p from its source (pass 0: `first`) into the other buffers
+    auto pass = [&](auto xq, uint32_t p, const LsdIo& io) -> int {
+        constexpr bool XQ = decltype(xq)::value;
+        r.begin(p == 0 ? SA_K_SCATTER_FIRST : SA_K_SCATTER_KEYS);
+        if (p == 0)
+            SA_TRY(lsd_pass<Src0, PACKED, XQ>(r, first, n, pl.shift[0], pl.bits[0], io));
+        else if constexpr (PACKED)
+            SA_TRY(lsd_pass<SrcItems, true, XQ>(r, SrcItems{kb[(p - 1) & 1]}, n, pl.shift[p], pl.bits[p], io));
+        else
+            SA_TRY(lsd_pass<SrcKeys, false, XQ>(r, SrcKeys{kb[(p - 1) & 1], vb[(p - 1) & 1]}, n, pl.shift[p],
+                                                pl.bits[p], io));
+        r.end();
+        r.bytes(p == 0 ? SA_K_SCATTER_FIRST : SA_K_SCATTER_KEYS, (p == 0 ? 8 + pair : 2 * pair) * n);
+        return SA_OK;
+    };
+    // per-XCD queues of tiles (sa_lsd.h XQ): counts [pass][8][1024], bases [8][1024], tickets [pass][8 x 32]
+    const bool xq = lsd_xq_ok(c, n, pl, PACKED);
+    const NextHist x = xq ? lsd_xq_span(n) : NextHist{};
+    uint32_t* const qh = c->lsdx;
+    uint32_t* const qb = qh + kMaxPasses * 8 * kLsdMaxRadix;
+    uint32_t* const qt = qb + 8 * kLsdMaxRadix;
+    if (xq && hist_ready) {   // pass 0's counts came with the previous round's re-rank
+        SA_HIP(hipMemsetAsync(c->lsdx + 8 * kLsdMaxRadix, 0, (kLsdXqWords - 8 * kLsdMaxRadix) * 4, s));
+    } else {
+        if (xq) SA_HIP(hipMemsetAsync(c->lsdx, 0, kLsdXqWords * 4, s));
+        r.begin(SA_K_HIST_FIRST);
+        if (xq) hipLaunchKernelGGL(k_lsd_hist<Src0>, hgrid, dim3(kBlock), 0, s, first, n, first_only, qh, x.qd);
+        else hipLaunchKernelGGL(k_lsd_hist<Src0>, hgrid, dim3(kBlock), 0, s, first, n, first_only, lsd_ghist(c));
+        r.end();
+        r.bytes(SA_K_HIST_FIRST, 8 * n);
+    }
+    for (uint32_t p = 0; p < pl.P; ++p) {
+        uint32_t* const base = xq ? qb : lsd_base(c) + p * kLsdMaxRadix;
+        r.begin(SA_K_SCAN);
+        if (xq)
             hipLaunchKernelGGL(k_lsd_qbase, dim3(1), dim3(1024), 0, s, (const uint32_t*)qh + p * 8 * kLsdMaxRadix,
                                1u << pl.bits[p], qb);
-            tm.end();
-            const bool more = p + 1 < pl.P;
-            const uint32_t nsh = more ? pl.shift[p + 1] : 0u, nnb = more ? pl.bits[p + 1] : 1u;
-            uint32_t* nh = more ? qh + (p + 1) * 8 * kLsdMaxRadix : nullptr;
-            uint32_t* tk = qt + p * 8 * 32;
-            if (p == 0) {
-                tm.begin(SA_K_SCATTER_FIRST);
-                SA_TRY(lsd_pass<Src0, PACKED, true>(c, first, n, pl.shift[0], pl.bits[0], qb, tk, kb[0], vb[0], s, nsh,
-                                                    nnb, nh, qd, tpq));
-                tm.end();
-                add_bytes(st, SA_K_SCATTER_FIRST, (8 + pair) * n);
-            } else {
-                tm.begin(SA_K_SCATTER_KEYS);
-                if constexpr (PACKED)
-                    SA_TRY(lsd_pass<SrcItems, true, true>(c, SrcItems{kb[(p - 1) & 1]}, n, pl.shift[p], pl.bits[p], qb,
-                                                          tk, kb[p & 1], nullptr, s, nsh, nnb, nh, qd, tpq));
-                else
-                    SA_TRY(lsd_pass<SrcKeys, false, true>(c, SrcKeys{kb[(p - 1) & 1], vb[(p - 1) & 1]}, n, pl.shift[p],
-                                                          pl.bits[p], qb, tk, kb[p & 1], vb[p & 1], s, nsh, nnb, nh,
-                                                          qd, tpq));
-                tm.end();
-                add_bytes(st, SA_K_SCATTER_KEYS, 2 * pair * n);
-            }
-        }
-        SA_HIP(hipGetLastError());
-        *sorted = kb[(pl.P - 1) & 1];
-        return SA_OK;
-    }
-    tm.begin(SA_K_HIST_FIRST);
-    hipLaunchKernelGGL(k_lsd_hist<Src0>, dim3((uint32_t)std::min<uint64_t>((n + 8 * kBlock - 1) / (8 * kBlock),
-                                                                           (uint64_t)c->cus * 4)),
-                       dim3(kBlock), 0, s, first, n, first_only, lsd_ghist(c));
-    tm.end();
-    add_bytes(st, SA_K_HIST_FIRST, 8 * n);
-    const uint64_t pair = PACKED ? 8 : 12;
-    for (uint32_t p = 0; p < pl.P; ++p) {
-        uint32_t* base = lsd_base(c) + p * kLsdMaxRadix;
-        tm.begin(SA_K_SCAN);
-        hipLaunchKernelGGL(k_digit_base_wide, dim3(1), dim3(1024), 0, s,
-                           (const uint32_t*)lsd_ghist(c) + p * kLsdMaxRadix, 1u << pl.bits[p], base);
-        tm.end();
+        else
+            hipLaunchKernelGGL(k_digit_base_wide, dim3(1), dim3(1024), 0, s,
+                               (const uint32_t*)lsd_ghist(c) + p * kLsdMaxRadix, 1u << pl.bits[p], base);
+        r.end();
         const bool more = p + 1 < pl.P;
-        const uint32_t nsh = more ? pl.shift[p + 1] : 0u, nnb = more ? pl.bits[p + 1] : 1u;
-        uint32_t* nh = more ? lsd_ghist(c) + (p + 1) * kLsdMaxRadix : nullptr;
-        if (p == 0) {
-            tm.begin(SA_K_SCATTER_FIRST);
-            SA_TRY(lsd_pass<Src0, PACKED>(c, first, n, pl.shift[0], pl.bits[0], base, lsd_tickets(c), kb[0], vb[0], s,
-                                          nsh, nnb, nh));
-            tm.end();
-            add_bytes(st, SA_K_SCATTER_FIRST, (8 + pair) * n);
-        } else {
-            tm.begin(SA_K_SCATTER_KEYS);
-            if constexpr (PACKED)
-                SA_TRY(lsd_pass<SrcItems, true>(c, SrcItems{kb[(p - 1) & 1]}, n, pl.shift[p], pl.bits[p], base,
-                                                lsd_tickets(c) + p, kb[p & 1], nullptr, s, nsh, nnb, nh));
-            else
-                SA_TRY(lsd_pass<SrcKeys, false>(c, SrcKeys{kb[(p - 1) & 1], vb[(p - 1) & 1]}, n, pl.shift[p],
-                                                pl.bits[p], base, lsd_tickets(c) + p, kb[p & 1], vb[p & 1], s, nsh,
-                                                nnb, nh));
-            tm.end();
-            add_bytes(st, SA_K_SCATTER_KEYS, 2 * pair * n);
-        }
+        uint32_t* const counts = xq ? qh + (p + 1) * 8 * kLsdMaxRadix : lsd_ghist(c) + (p + 1) * kLsdMaxRadix;
+        const LsdIo io{base, xq ? qt + p * 8 * 32 : lsd_tickets(c) + p, kb[p & 1], PACKED && p ? nullptr : vb[p & 1],
+                       more ? pl.shift[p + 1] : 0u, more ? pl.bits[p + 1] : 1u, more ? counts : nullptr,
+                       x.qd, (uint32_t)(x.qspan / kLsdXqTile)};
+        if (xq) SA_TRY(pass(std::true_type{}, p, io));
+        else SA_TRY(pass(std::false_type{}, p, io));
     }
     SA_HIP(hipGetLastError());
-    *sorted = kb[(pl.P - 1) & 1];
+    *sorted = Sorted{kb[(pl.P - 1) & 1], pl.P};
     return SA_OK;
 }
 
-// round 1's first-digit counts taken by the init kernel (A/B switch)
-#ifndef SA_INIT_HIST
-#define SA_INIT_HIST 1
-#endif
-static int build_reference(sa_context* c, const uint8_t* d_text, uint64_t n, uint32_t* d_sa, hipStream_t s,
-                           sa_stats* st, Timer& tm) {
-    int rc = SA_OK;
-    const Chunking ch = plan_chunks(n);
-    // first ranks: dense codes 1..sigma of the bytes present (the order of
-    // manber_myers.c:90's text[i] + 1, so D_j and the round count are the
-    // reference's; the first key spans 2 bit_width(sigma) bits, not 18)
-    uint32_t* h_alpha = c->host_words + hw(kHwAlpha).at;
-    uint16_t* h_code = reinterpret_cast<uint16_t*>(c->host_words + hw(kHwCode).at);
-    SA_HIP(hipMemsetAsync(c->alpha, 0, 8 * 4, s));
-    tm.begin(SA_K_ALPHABET);
-    {
-        const uint32_t grid = (uint32_t)std::min<uint64_t>((n + kBlock * 16 - 1) / (kBlock * 16), SA_ALPHA_GRID);
-        hipLaunchKernelGGL(k_alphabet, dim3(grid), dim3(kBlock), 0, s, d_text, n, c->alpha);
-    }
-    tm.end();
-    add_bytes(st, SA_K_ALPHABET, n);
-    SA_HIP(hipMemcpyAsync(h_alpha, c->alpha, 8 * 4, hipMemcpyDeviceToHost, s));
-    SA_HIP(host_sync(s));
-    uint32_t sigma = 0;
-    for (int b = 0; b < 256; ++b) h_code[b] = ((h_alpha[b >> 5] >> (b & 31)) & 1u) ? (uint16_t)(++sigma) : 0;
-    SA_HIP(hipMemcpyAsync(c->code, h_code, 256 * 2, hipMemcpyHostToDevice, s));
-    uint64_t D = sigma;   // ranks 1..sigma (manber_myers.c:94 sizes its bins for 256)
-    const uint64_t perm_min = perm_min_n(c);
-    const uint32_t ib = std::max<uint32_t>(1, bit_width(n - 1));   // index bits of a packed item
-    bool used_perm = false;
-    bool hist_ready = false;   // this round's first-digit counts came with the previous re-rank (or the init)
-    tm.begin(SA_K_INIT);
-    {
-        // round 1's first-digit counts per XCD queue with the ranks (k_init_rank_hist)
-        const uint32_t w1 = bit_width(D);
-        const bool packed1 = c->radix == 0 && 2 * w1 + ib <= 64;
-        const LsdPlan pl1 = lsd_plan(2 * w1, packed1 ? ib : 0, lsd_max_bits(c));
-        if (SA_INIT_HIST && c->radix == 0 && lsd_xq_ok(c, n, pl1, packed1)) {
-            uint32_t tpq;
-            uint64_t qspan;
-            QDiv qd;
-            lsd_xq_span(n, &tpq, &qspan, &qd);
-            SA_HIP(hipMemsetAsync(c->lsdx, 0, 8 * kLsdMaxRadix * 4, s));
-            const uint64_t grid = std::min<uint64_t>((n + kBlock * 16 - 1) / (kBlock * 16), 4ull * (uint64_t)c->cus);
-            hipLaunchKernelGGL(k_init_rank_hist, dim3((uint32_t)grid), dim3(kBlock), 0, s, d_text, n,
-                               (const uint16_t*)c->code, c->rank, w1, pl1.shift[0] - (packed1 ? ib : 0u),
-                               (1u << pl1.bits[0]) - 1u, qd, c->lsdx);
-            hist_ready = true;
-        } else {
-            const uint64_t grid = std::min<uint64_t>((n + kBlock * 4 - 1) / (kBlock * 4), 4096);
-            hipLaunchKernelGGL(k_init_rank_dense, dim3((uint32_t)grid), dim3(kBlock), 0, s, d_text, n,
-                               (const uint16_t*)c->code, c->rank);
-        }
-    }
-    tm.end();
-    SA_HIP(hipGetLastError());
-    add_bytes(st, SA_K_INIT, 5 * n);
-    if (st) st->sigma = (int32_t)sigma;
+// the reference schedule: manber_myers.c:88-125 round for round
+#include "sa_reference.h"
 
-    tm.round_mark();
-    for (uint64_t h = 1;; h *= 2) {
-        const uint32_t w = bit_width(D);          // ranks are 0..D
-        // (key << ib | index) items while they fit 64 bits (onesweep only)
-        const bool packed = c->radix == 0 && 2 * w + ib <= 64;
-        SA_TRACE("reference round h=%llu D=%llu w=%u%s", (unsigned long long)h, (unsigned long long)D, w,
-                 packed ? " packed" : "");
-        SrcRank src{c->rank, n, h, w};
-        uint64_t* sorted;
-        uint32_t P;
-        if (c->radix == 0) {
-            const LsdPlan pl = lsd_plan(2 * w, packed ? ib : 0, lsd_max_bits(c));
-            P = pl.P;
-            rc = packed ? lsd_sort<true>(c, SrcRankPk{c->rank, n, h, w, ib}, n, pl, d_sa, c->vals_alt, s, tm, st,
-                                         &sorted, hist_ready)
-                        : lsd_sort<false>(c, src, n, pl, d_sa, c->vals_alt, s, tm, st, &sorted, hist_ready);
-        } else {
-            rc = radix_sort(c, src, 4 * n, ch, 2 * w, d_sa, c->vals_alt, c->keys[0], c->keys[1], s, tm, st, &sorted,
-                            &P);
-        }
-        if (rc) return rc;
-        // the permutation's first level counts heads per tile of its own
-        const bool use_perm = packed || n >= perm_min;
-        const uint32_t ptiles = (uint32_t)((n + kPermTile - 1) / kPermTile);
-        tm.begin(SA_K_HEADS);
-        if (use_perm)
-            hipLaunchKernelGGL((k_tile_heads<kPermBlock, kPermItems>), dim3(ptiles), dim3(kPermBlock), 0, s,
-                               (const uint64_t*)sorted, n, packed ? ib : 0u, perm_tile_off(c));
-        else
-            hipLaunchKernelGGL(k_heads, dim3(ch.chunks), dim3(kBlock), 0, s, sorted, ch, c->counts, 0u);
-        tm.end();
-        tm.begin(SA_K_HEADS_SCAN);
-        if (use_perm)
-            hipLaunchKernelGGL(k_scan_heads, dim3(1), dim3(kBlock), 0, s, perm_tile_off(c), ptiles, c->words);
-        else
-            hipLaunchKernelGGL(k_scan_heads, dim3(1), dim3(kBlock), 0, s, c->counts, ch.chunks, c->words);
-        tm.end();
-        SA_HIP(hipGetLastError());
-        add_bytes(st, SA_K_HEADS, 8 * n);
-        add_bytes(st, SA_K_HEADS_SCAN, 8ull * ch.chunks);
-        // (with the permutation re-rank's error word: the previous round's
-        // placement is checked before this round's ranks are used)
-        SA_HIP(hipMemcpyAsync(c->host_words, c->words, 4 * (kPermErrWord + 1), hipMemcpyDeviceToHost, s));
-        SA_HIP(host_sync(s));
-        if (c->host_words[4]) return set_err(SA_E_INTERNAL, "radix look-back did not complete");
-        if (used_perm && c->host_words[kPermErrWord])
-            return set_err(SA_E_INTERNAL, "re-rank permutation lost a suffix (flags %u)", c->host_words[kPermErrWord]);
-        const uint64_t Dn = c->host_words[0];
-        const bool done = (Dn == n);                  // manber_myers.c:113
-        if (done && packed) {
-            tm.begin(SA_K_RERANK);
-            hipLaunchKernelGGL(k_items_to_sa, dim3((uint32_t)std::min<uint64_t>((n + kBlock - 1) / kBlock, 8192)),
-                               dim3(kBlock), 0, s, (const uint64_t*)sorted, n, ib, d_sa);
-            tm.end();
-            SA_HIP(hipGetLastError());
-            add_bytes(st, SA_K_RERANK, 12 * n);
-        }
-        hist_ready = false;
-        if (!done) {
-            if (use_perm) {
-                used_perm = true;
-                // the next round's first digit lies in rank[i + 2h] alone (its
-                // width <= w'): the re-rank counts it per queue of that round's
-                // LSD passes while it writes rank[] (no histogram read then)
-                NextHist nh;
-                if (c->radix == 0) {
-                    const uint32_t w2 = bit_width(Dn);
-                    const bool packed2 = 2 * w2 + ib <= 64;
-                    const LsdPlan pl2 = lsd_plan(2 * w2, packed2 ? ib : 0, lsd_max_bits(c));
-                    if (pl2.bits[0] <= w2 && lsd_xq_ok(c, n, pl2, packed2)) {
-                        uint32_t tpq;
-                        lsd_xq_span(n, &tpq, &nh.qspan, &nh.qd);
-                        nh.out = c->lsdx;
-                        nh.mask = (1u << pl2.bits[0]) - 1u;
-                        nh.h = 2 * h;
-                        hist_ready = true;
-                    }
-                }
-                rc = rerank_permute(c, sorted, d_sa, ch, s, tm, st, packed ? ib : 0u, nh);
-                if (rc) return rc;
-            } else {
-                tm.begin(SA_K_RERANK);
-                hipLaunchKernelGGL(k_rerank, dim3(ch.chunks), dim3(kBlock), 0, s, sorted, (const uint32_t*)d_sa, ch,
-                                   (const uint32_t*)c->counts, c->rank);
-                tm.end();
-                SA_HIP(hipGetLastError());
-                add_bytes(st, SA_K_RERANK, 16 * n);
-            }
-        }
-        tm.round_mark();
-        record_round(st, 0.f, Dn, P, n, 2 * h);   // (its time: Timer::round_times)
-        if (Dn > n || Dn == 0)
-            return set_err(SA_E_INTERNAL, "distinct count %llu out of range", (unsigned long long)Dn);
-        if (done) break;
-        if (h > n) return set_err(SA_E_INTERNAL, "doubling did not converge (h=%llu)", (unsigned long long)h);
-        D = Dn;
-    }
-    if (used_perm) {
-        SA_HIP(hipMemcpyAsync(c->host_words + kPermErrWord, c->words + kPermErrWord, 4, hipMemcpyDeviceToHost, s));
-        SA_HIP(host_sync(s));
-        if (c->host_words[kPermErrWord])
-            return set_err(SA_E_INTERNAL, "re-rank permutation lost a suffix (flags %u)", c->host_words[kPermErrWord]);
-    }
-    return SA_OK;
-}
-
-// ---------------------------------------------------------------------------
-// packed schedule
-// ---------------------------------------------------------------------------
-// K for base B: largest K with B^K - 1 < 2^64
-static uint32_t max_chars(uint64_t base) {
-    uint32_t K = 0;
-    uint64_t prod = 1;
-    while (prod <= UINT64_MAX / base) {
-        prod *= base;
-        ++K;
-    }
-    return K;
-}
-
-static uint32_t key_bits(uint64_t base, uint32_t K) {   // bit width of B^K - 1
-    unsigned __int128 p = 1;
-    for (uint32_t t = 0; t < K; ++t) p *= base;
-    p -= 1;
-    uint32_t w = 0;
-    while (p) { ++w; p >>= 1; }
-    return w;
-}
-
-// the fewest symbols K with sigma^K >= 512 n: a random text of this
-// alphabet then leaves few suffixes unsorted by round 1
-static uint32_t min_chars(uint32_t sigma, uint64_t n) {
-    const uint32_t kmax = max_chars((uint64_t)sigma + 1);
-    uint32_t kmin = 1;
-    unsigned __int128 p = sigma, target = (unsigned __int128)n * 512u;
-    while (p < target && kmin < kmax) {
-        p *= sigma;
-        ++kmin;
-    }
-    return kmin;
-}
-
-// auto K: min_chars, rounded up to fill the radix passes (the LSD round 1).
-static uint32_t choose_chars(uint32_t sigma, uint64_t n, int32_t req) {
-    const uint64_t base = (uint64_t)sigma + 1;
-    const uint32_t kmax = max_chars(base);
-    if (req > 0) return std::min<uint32_t>((uint32_t)req, kmax);
-    if (sigma <= 1) return kmax;
-    const uint32_t kmin = min_chars(sigma, n);
-    const uint32_t P = (key_bits(base, kmin) + 7) / 8;
-    uint32_t K = kmin;
-    while (K + 1 <= kmax && key_bits(base, K + 1) <= 8 * P) ++K;
-    return K;
-}
-
-// unsorted-set rounds try the per-group register sort when the average
-// group holds at most kUsAvg suffixes; its oversize flag lives in words[12]
-constexpr uint64_t kUsAvg = 4;
-// per-group register sort over keys materialised one lane per suffix first
-#ifndef SA_US_TWO_PHASE
-#define SA_US_TWO_PHASE 1
-#endif
-
-template <class Pos>
-static int segments(sa_context* c, const uint64_t* keys, const uint32_t* idx, const Chunking& ch, Pos pos,
-                    bool sparse_ok, bool* sparse_out,
-                    uint32_t* sa, int uo, hipStream_t s, Timer& tm, sa_stats* st, uint64_t* D, uint64_t* m,
-                    uint64_t* G, uint32_t* rank_arr = nullptr, uint64_t rank_off = 0, RankMap rm = RankMap{},
-                    uint64_t set_off = 0, uint32_t g_off = 0, uint32_t* gsn = nullptr) {
-    // rank_arr / rank_off / rm: the range-partitioned build's compact rank map
-    // and its SA offset (sa_dist.h); the context's rank array, 0 and the
-    // identity map on one GPU.  set_off / g_off: the next unsorted set's
-    // first slot and group id (the tied-block round's rest, sa_pivot.h)
-    if (!rank_arr) rank_arr = c->rank;
-    uint32_t* c_h = c->counts;
-    uint32_t* c_u = c->counts + kMaxChunks;
-    uint32_t* c_uh = c->counts + 2 * kMaxChunks;
-    uint32_t* c_l = c->counts + 3 * kMaxChunks;
-    tm.begin(SA_K_SEG_COUNT);
-    hipLaunchKernelGGL(k_seg_count, dim3(ch.chunks), dim3(kBlock), 0, s, keys, ch, c_h, c_u, c_uh, c_l);
-    tm.end();
-    tm.begin(SA_K_SEG_SCAN);
-    hipLaunchKernelGGL(k_seg_scan, dim3(1), dim3(kBlock), 0, s, c_h, c_u, c_uh, c_l, ch.chunks, c->words);
-    tm.end();
-    SA_HIP(hipGetLastError());
-    SA_HIP(hipMemcpyAsync(c->host_words, c->words, 20, hipMemcpyDeviceToHost, s));
-    SA_HIP(host_sync(s));
-    if (c->host_words[4]) return set_err(SA_E_INTERNAL, "radix look-back did not complete");
-    *D = c->host_words[0];
-    *m = c->host_words[1];
-    *G = c->host_words[2];
-    // first round with few unsorted suffixes: keep ranks only for those
-    const bool sparse = sparse_ok && *m <= ch.n / kSparseDiv;
-    uint32_t* member = nullptr;
-    if (sparse) {
-        SA_HIP(hipMemsetAsync(c->member, 0, (ch.n + 31) / 32 * 4, s));
-        member = c->member;
-    }
-    if (sparse_out) *sparse_out = sparse;
-    tm.begin(SA_K_SEG_WRITE);
-    hipLaunchKernelGGL(k_seg_write<Pos>, dim3(ch.chunks), dim3(kBlock), 0, s, keys, idx, ch, pos,
-                       (const uint32_t*)c_u, (const uint32_t*)c_uh, (const uint32_t*)c_l, rank_arr, sa,
-                       c->u_pos[uo] + set_off, c->u_idx[uo] + set_off, c->u_g[uo] + set_off, member, sparse ? 0 : 1,
-                       (uint32_t)rank_off, rm, g_off, gsn ? gsn + g_off : nullptr, (uint32_t)set_off);
-    tm.end();
-    SA_HIP(hipGetLastError());
-    add_bytes(st, SA_K_SEG_COUNT, 8 * ch.n);
-    add_bytes(st, SA_K_SEG_SCAN, 32ull * ch.chunks);
-    add_bytes(st, SA_K_SEG_WRITE, ch.n * (8 + (sparse ? 0 : 8)) + (sa ? 8 * ch.n : 0) + *m * 16);
-    return SA_OK;
-}
-
-// Unsorted-set round by a three-way pivot split (sa_pivot.h): dense ranks,
-// large groups on average.  Returns SA_OK with *sorted = nullptr when the
-// tied blocks turn out small (the caller then sorts the whole set).
-static bool pivot_ok(const sa_context* c, uint64_t m, uint64_t G, uint32_t wr, bool sparse) {
-    return !(c->dbg & SA_DEBUG_NO_PIVOT) && c->radix == 0 && !sparse && m >= (1u << 16) && G >= 1 && G <= m / 4 && bit_width(2 * G + 1) + wr <= 64;
-}
-
-// keys + class counts of a pivot round in one pass when the set came with its
-// group starts (sa_pivot.h MODE 1; A/B switch)
-#ifndef SA_PIVOT_MERGED
-#define SA_PIVOT_MERGED 1
-#endif
-// tied-block rounds (sa_pivot.h) scan the groups in one workgroup
-constexpr uint64_t kPivotTiedMaxG = 1u << 18;
-
-static int pivot_round(sa_context* c, int ui, int uo, uint64_t n, uint64_t m, uint64_t G, uint64_t h, uint32_t wr,
-                       uint64_t* ukb0, uint64_t* ukb1, uint64_t* kbA, const Chunking& cu, uint32_t* d_sa,
-                       hipStream_t s, Timer& tm, sa_stats* st, uint64_t** sorted, uint32_t* P, bool* segs_done,
-                       uint64_t* Du, uint64_t* m2, uint64_t* G2, bool have_gs, bool* gs_written) {
-    // have_gs: the set's group starts are in u_gs[ui] (written with it by the
-    // previous round); *gs_written: this round wrote the next set's to u_gs[uo]
-    *sorted = nullptr;
-    *segs_done = false;
-    *gs_written = false;
-    // tied-block round: its scratch is ukb0 (free: the tied members skip the
-    // sorted output) -- gs, pr, toff, tid, then the rest's values (3 x
-    // m' <= 3 m / 2 words)
-    const uint64_t scap = 2 * align_up(c->cap, 64);
-    const uint64_t sbase = align_up(4 * G + 3, 64);
-    const uint64_t ra_max = align_up(m / 2, 64);
-    // tied blocks write the next set's group starts: u_gs is allocated here,
-    // and a workspace too tight for it takes the split path (k_pivot_pass<2>,
-    // no extra memory) instead of failing the build
-    const bool tied = !(c->dbg & SA_DEBUG_NO_TIED) && G <= kPivotTiedMaxG && sbase + 3 * ra_max <= scap &&
-                      gs_available(c, n);
-    uint32_t* const scr = reinterpret_cast<uint32_t*>(ukb0);
-    const bool merged = SA_PIVOT_MERGED && tied && have_gs;
-    uint32_t* const gs = merged ? c->u_gs[ui] : tied ? scr : c->u_pos[uo];   // G (+ 1) group starts
-    uint32_t* const pr = (tied ? scr : gs) + G + 1;                          // G pivot ranks
-    uint32_t* const gP = c->vals_alt;                 // 3 (G + 1): members of each class before each group
-    uint32_t* const cc = c->hist;                     // 3 x chunks class counts, scanned in place
-    const uint32_t Gu = (uint32_t)G;
-    if (merged) {
-        // the group starts came with the set: keys built and classes counted
-        // in one pass (MODE 1: k_pivot_keys + MODE 0)
-        tm.begin(SA_K_PIVOT_COUNT);
-        PivotKeySrc ks;
-        ks.rank = c->rank;
-        ks.n = n;
-        ks.h = h;
-        ks.keys_out = ukb1;
-        ks.pr_out = pr;
-        hipLaunchKernelGGL(k_pivot_pass<1>, dim3(cu.chunks), dim3(kBlock), 0, s, (const uint64_t*)nullptr,
-                           (const uint32_t*)c->u_idx[ui], (const uint32_t*)c->u_g[ui], cu, (const uint32_t*)gs,
-                           (const uint32_t*)pr, Gu, wr, cc, gP, nullptr, nullptr, nullptr, nullptr, TiedOut{}, ks);
-        hipLaunchKernelGGL(k_scan_rows, dim3(3), dim3(kBlock), 0, s, cc, cu.chunks, c->totals);
-        tm.end();
-        SA_HIP(hipGetLastError());
-        add_bytes(st, SA_K_PIVOT_COUNT, 20 * m);
-    } else {
-        tm.begin(SA_K_PIVOT_KEYS);
-        hipLaunchKernelGGL(k_pivot_keys,
-                           dim3((uint32_t)std::min<uint64_t>((m + kBlock * kPkItems - 1) / (kBlock * kPkItems), 8192)),
-                           dim3(kBlock), 0, s, (const uint32_t*)c->u_idx[ui], (const uint32_t*)c->u_g[ui], m,
-                           (const uint32_t*)c->rank, n, h, wr, Gu, ukb1, gs, pr);
-        tm.end();
-        add_bytes(st, SA_K_PIVOT_KEYS, 20 * m);
-        tm.begin(SA_K_PIVOT_COUNT);
-        hipLaunchKernelGGL(k_pivot_pass<0>, dim3(cu.chunks), dim3(kBlock), 0, s, (const uint64_t*)ukb1,
-                           (const uint32_t*)c->u_idx[ui], (const uint32_t*)c->u_g[ui], cu, (const uint32_t*)gs,
-                           (const uint32_t*)pr, Gu, wr, cc, gP, nullptr, nullptr, nullptr, nullptr, TiedOut{});
-        hipLaunchKernelGGL(k_scan_rows, dim3(3), dim3(kBlock), 0, s, cc, cu.chunks, c->totals);
-        tm.end();
-        SA_HIP(hipGetLastError());
-        add_bytes(st, SA_K_PIVOT_COUNT, 8 * m);
-    }
-    SA_HIP(hipMemcpyAsync(c->host_words + hw(kHwTotals).at, c->totals, 12, hipMemcpyDeviceToHost, s));
-    SA_HIP(host_sync(s));
-    const uint32_t* ht = c->host_words + hw(kHwTotals).at;
-    const uint64_t t0 = ht[0], t1 = ht[1], t2 = ht[2];
-    if (t0 + t1 + t2 != m) return set_err(SA_E_INTERNAL, "pivot classes %llu + %llu + %llu != %llu",
-                                          (unsigned long long)t0, (unsigned long long)t1, (unsigned long long)t2,
-                                          (unsigned long long)m);
-    SA_TRACE("  round h=%llu: pivot split, tied %llu of %llu%s", (unsigned long long)h, (unsigned long long)t1,
-             (unsigned long long)m, tied ? " (tied blocks to the next set)" : "");
-    if (t1 * 2 < m) return SA_OK;   // mostly distinct keys: the full sort is cheaper
-    tm.begin(SA_K_PIVOT_WRITE);
-    hipLaunchKernelGGL(k_pivot_gp, dim3((uint32_t)std::min<uint64_t>((G + kBlock) / kBlock, 8192)), dim3(kBlock), 0, s,
-                       (const uint32_t*)gs, Gu, (const uint32_t*)cc, cu, (const uint32_t*)c->totals, gP);
-    const uint64_t mr = t0 + t2;
-    const uint64_t ra = align_up(mr, 64);
-    uint32_t* const ridx = tied ? scr + sbase : c->u_idx[uo];
-    uint64_t T = 0, Gt = 0, Dt = 0;
-    if (tied) {
-        // the next set's group starts go with it (the next pivot round's MODE 1;
-        // u_gs allocated by gs_available above)
-        uint32_t* const toff = scr + 2 * G + 1;
-        uint32_t* const tid = toff + G + 1;
-        hipLaunchKernelGGL(k_pivot_tied_scan, dim3(1), dim3(kBlock), 0, s, (const uint32_t*)gP, Gu, toff, tid,
-                           c->totals + 4);
-        const TiedOut to{c->u_pos[ui], toff, tid, c->rank, d_sa, c->u_pos[uo], c->u_idx[uo], c->u_g[uo], c->u_gs[uo]};
-        hipLaunchKernelGGL(k_pivot_pass<3>, dim3(cu.chunks), dim3(kBlock), 0, s, (const uint64_t*)ukb1,
-                           (const uint32_t*)c->u_idx[ui], (const uint32_t*)c->u_g[ui], cu, (const uint32_t*)gs,
-                           (const uint32_t*)pr, Gu, wr, cc, gP, nullptr, nullptr, kbA, ridx, to);
-    } else {
-        hipLaunchKernelGGL(k_pivot_pass<2>, dim3(cu.chunks), dim3(kBlock), 0, s, (const uint64_t*)ukb1,
-                           (const uint32_t*)c->u_idx[ui], (const uint32_t*)c->u_g[ui], cu, (const uint32_t*)gs,
-                           (const uint32_t*)pr, Gu, wr, cc, gP, ukb0, c->vals_u, kbA, ridx, TiedOut{});
-    }
-    tm.end();
-    SA_HIP(hipGetLastError());
-    add_bytes(st, SA_K_PIVOT_WRITE, tied ? 12 * m + 16 * t1 + 12 * mr : 12 * m + 12 * m);
-    if (tied) {
-        SA_HIP(hipMemcpyAsync(c->host_words + hw(kHwUTotals).at, c->totals + 4, 12, hipMemcpyDeviceToHost, s));
-        SA_HIP(host_sync(s));
-        T = c->host_words[hw(kHwUTotals).at];
-        Gt = c->host_words[hw(kHwUTotals).at + 1];
-        Dt = c->host_words[hw(kHwUTotals).at + 2];
-        if (T > t1 || Gt > G || Dt > G)
-            return set_err(SA_E_INTERNAL, "tied blocks %llu / %llu / %llu out of range", (unsigned long long)T,
-                           (unsigned long long)Gt, (unsigned long long)Dt);
-    }
-    uint32_t Pr = 0;
-    uint64_t Dr = 0, mrr = 0, Gr = 0;
-    if (mr > 0) {
-        // the rest sorted by (2 g + [> pivot], rank): values in u_idx / u_g
-        // of the next set (free until segments()) or the tied round's
-        // scratch, keys through kbA and ukb1
-        const uint32_t bits = bit_width(2 * G - 1) + wr;
-        const uint32_t Pn = (bits + 7) / 8;
-        uint32_t* const va = tied ? ridx + ra : c->u_g[uo];
-        uint32_t* const vb = tied ? ridx + 2 * ra : c->u_idx[uo];
-        uint32_t* vfinal = (Pn & 1u) ? va : vb;
-        uint32_t* vother = (Pn & 1u) ? vb : va;
-        uint64_t* rs = nullptr;
-        int rc = radix_sort(c, SrcKeys{kbA, ridx}, 12 * mr, plan_chunks(mr), bits, vfinal, vother, ukb1, kbA, s, tm,
-                            st, &rs, &Pr, false, true);
-        if (rc) return rc;
-        tm.begin(SA_K_SORT_U);
-        const dim3 pg((uint32_t)std::min<uint64_t>((mr + kBlock - 1) / kBlock, 8192));
-        if (tied)
-            hipLaunchKernelGGL(k_pivot_place<true>, pg, dim3(kBlock), 0, s, (const uint64_t*)rs,
-                               (const uint32_t*)vfinal, mr, (const uint32_t*)gs, (const uint32_t*)gP, Gu, wr, nullptr,
-                               nullptr, m, (const uint32_t*)c->u_pos[ui], c->vals_u);
-        else
-            hipLaunchKernelGGL(k_pivot_place<false>, pg, dim3(kBlock), 0, s, (const uint64_t*)rs,
-                               (const uint32_t*)vfinal, mr, (const uint32_t*)gs, (const uint32_t*)gP, Gu, wr, ukb0,
-                               c->vals_u, m, nullptr, nullptr);
-        tm.end();
-        SA_HIP(hipGetLastError());
-        add_bytes(st, SA_K_SORT_U, tied ? 20 * mr : 24 * mr);
-        if (tied) {
-            // the rest's segments, appended to the next set after the tied blocks
-            rc = segments(c, rs, vfinal, plan_chunks(mr), PosArray{c->vals_u}, false, nullptr, d_sa, uo, s, tm, st,
-                          &Dr, &mrr, &Gr, nullptr, 0, RankMap{}, T, (uint32_t)Gt, c->u_gs[uo]);
-            if (rc) return rc;
-        }
-    }
-    *P = 1 + Pr;
-    if (tied) {
-        *gs_written = true;
-        *segs_done = true;
-        *Du = Dr + Dt;
-        *m2 = mrr + T;
-        *G2 = Gr + Gt;
-    }
-    *sorted = ukb0;
-    return SA_OK;
-}
-
-// Round 1 by the pivot split (sa_pivot.h, R1): when the LSD round 1 would
-// run and at least half of all suffixes share the key of suffix 0 (a text of
-// one repeated symbol, configs[4]: all but the last K), those form one tied
-// block -- ranks and the next unsorted set written directly -- and only the
-// rest is radix sorted (then segments() over it, SA positions around the
-// block's gap).  *done = false (nothing written but the class counts) when
-// fewer share it: the caller runs the LSD sort.
-static int pivot_round1(sa_context* c, uint64_t n, uint32_t bits1, uint32_t* d_sa, hipStream_t s, Timer& tm,
-                        sa_stats* st, bool* done, uint64_t* D, uint64_t* m, uint64_t* G, uint32_t* P) {
-    *done = false;   // (done: the set's group starts are in u_gs[0] too)
-    const Chunking ch = plan_chunks(n);
-    const uint64_t* keys = c->keys[1];
-    uint32_t* const gs = c->u_pos[1];   // {0, n}: one group
-    uint32_t* const toff = gs + 2;
-    uint32_t* const tid = gs + 4;
-    uint32_t* const gP = c->vals_alt;   // 3 x 2
-    uint32_t* const cc = c->hist;       // 3 x chunks class counts
-    uint32_t* hg = c->host_words + hw(kHwGsInit).at;
-    hg[0] = 0;
-    hg[1] = (uint32_t)n;
-    SA_HIP(hipMemcpyAsync(gs, hg, 8, hipMemcpyHostToDevice, s));
-    tm.begin(SA_K_PIVOT_COUNT);
-    hipLaunchKernelGGL((k_pivot_pass<0, true>), dim3(ch.chunks), dim3(kBlock), 0, s, keys, nullptr, nullptr, ch,
-                       (const uint32_t*)gs, nullptr, 1u, 0u, cc, gP, nullptr, nullptr, nullptr, nullptr, TiedOut{});
-    hipLaunchKernelGGL(k_scan_rows, dim3(3), dim3(kBlock), 0, s, cc, ch.chunks, c->totals);
-    tm.end();
-    SA_HIP(hipGetLastError());
-    add_bytes(st, SA_K_PIVOT_COUNT, 8 * n);
-    SA_HIP(hipMemcpyAsync(c->host_words + hw(kHwTotals).at, c->totals, 12, hipMemcpyDeviceToHost, s));
-    SA_HIP(host_sync(s));
-    const uint32_t* ht = c->host_words + hw(kHwTotals).at;
-    const uint64_t t0 = ht[0], t1 = ht[1], t2 = ht[2];
-    if (t0 + t1 + t2 != n) return set_err(SA_E_INTERNAL, "round-1 pivot classes %llu + %llu + %llu != %llu",
-                                          (unsigned long long)t0, (unsigned long long)t1, (unsigned long long)t2,
-                                          (unsigned long long)n);
-    SA_TRACE("  round 1: pivot split, tied %llu of %llu", (unsigned long long)t1, (unsigned long long)n);
-    if (t1 * 2 < n) return SA_OK;
-    const uint64_t mr = t0 + t2;
-    // the rest: keys -> keys[0], values ping-pong in u_idx[1] / u_g[1] (the
-    // next set goes to u_*[0]), key buffers keys_u / keys[0]
-    uint64_t* const rk = c->keys[0];
-    uint32_t* const ridx = c->u_idx[1];
-    // the set's group starts, for round 2's MODE 1; without room for them
-    // round 1 keeps the LSD sort (*done = false: nothing written yet)
-    if (!gs_available(c, n)) return SA_OK;
-    tm.begin(SA_K_PIVOT_WRITE);
-    hipLaunchKernelGGL(k_pivot_gp, dim3(1), dim3(kBlock), 0, s, (const uint32_t*)gs, 1u, (const uint32_t*)cc, ch,
-                       (const uint32_t*)c->totals, gP);
-    hipLaunchKernelGGL(k_pivot_tied_scan, dim3(1), dim3(kBlock), 0, s, (const uint32_t*)gP, 1u, toff, tid,
-                       c->totals + 4);
-    const TiedOut to{nullptr, toff, tid, c->rank, d_sa, c->u_pos[0], c->u_idx[0], c->u_g[0], c->u_gs[0]};
-    hipLaunchKernelGGL((k_pivot_pass<3, true>), dim3(ch.chunks), dim3(kBlock), 0, s, keys, nullptr, nullptr, ch,
-                       (const uint32_t*)gs, nullptr, 1u, 0u, cc, gP, nullptr, nullptr, rk, ridx, to);
-    tm.end();
-    SA_HIP(hipGetLastError());
-    add_bytes(st, SA_K_PIVOT_WRITE, 8 * n + 16 * t1 + 12 * mr);
-    SA_HIP(hipMemcpyAsync(c->host_words + hw(kHwUTotals).at, c->totals + 4, 12, hipMemcpyDeviceToHost, s));
-    SA_HIP(host_sync(s));
-    const uint32_t* hu = c->host_words + hw(kHwUTotals).at;
-    const uint64_t T = hu[0], Gt = hu[1], Dt = hu[2];
-    if (T > t1 || Gt > 1 || Dt > 1)
-        return set_err(SA_E_INTERNAL, "round-1 tied block %llu / %llu / %llu out of range", (unsigned long long)T,
-                       (unsigned long long)Gt, (unsigned long long)Dt);
-    uint32_t Pr = 0;
-    uint64_t Dr = 0, mrr = 0, Gr = 0;
-    if (mr > 0) {
-        const uint32_t Pn = (bits1 + 7) / 8;
-        uint32_t* const vfinal = (Pn & 1u) ? c->u_g[1] : ridx;
-        uint32_t* const vother = (Pn & 1u) ? ridx : c->u_g[1];
-        uint64_t* rs = nullptr;
-        int rc = radix_sort(c, SrcKeys{rk, ridx}, 12 * mr, plan_chunks(mr), bits1, vfinal, vother, c->keys_u, rk, s,
-                            tm, st, &rs, &Pr);
-        if (rc) return rc;
-        rc = segments(c, rs, vfinal, plan_chunks(mr), PosGap{t0, t1}, false, nullptr, d_sa, 0, s, tm, st, &Dr, &mrr,
-                      &Gr, nullptr, 0, RankMap{}, T, (uint32_t)Gt, c->u_gs[0]);
-        if (rc) return rc;
-    }
-    *done = true;
-    *D = Dr + Dt;
-    *m = mrr + T;
-    *G = Gr + Gt;
-    *P = 2 + Pr;
-    return SA_OK;
-}
-
-static int build_packed(sa_context* c, const uint8_t* d_text, uint64_t n, uint32_t* d_sa, hipStream_t s,
-                        const sa_opts* opts, sa_stats* st, Timer& tm) {
-    int rc = SA_OK;
-    rc = ensure_u_capacity(c, n);
-    if (rc) return rc;
-    tm.round_mark();
-    uint32_t* h_alpha = c->host_words + hw(kHwAlpha).at;
-    uint16_t* h_code = reinterpret_cast<uint16_t*>(c->host_words + hw(kHwCode).at);
-    // the text's last bytes: the compact key layout's check (short_suffix_ties)
-    const uint32_t tail_n = (uint32_t)std::min<uint64_t>(n, (uint64_t)kMaxK);
-    uint8_t* h_tail = reinterpret_cast<uint8_t*>(c->host_words + hw(kHwTail).at);
-    uint32_t sigma = 0, K = 0, Kb = 0;
-    BucketPlan bp;
-    const int r1 = opts ? opts->round1 : SA_ROUND1_AUTO;
-    bool bucketed = false;
-    // alphabet -> dense codes (host reads the 256-bit presence mask) -> the
-    // plan of round 1.  sampled: the mask of a sample of the text
-    // (sa_alpha.h) instead of a pass over all of it; *complete = false when
-    // the text's tail holds a byte the sample missed.
-    auto plan_round1 = [&](bool sampled, bool* complete) -> int {
-        SA_HIP(hipMemsetAsync(c->alpha, 0, 8 * 4, s));
-        tm.begin(SA_K_ALPHABET);
-        if (sampled) {
-            const bool first4k = (c->dbg & SA_DEBUG_ALPHA_SAMPLE_SMALL) != 0;
-            const uint64_t nb = alpha_text_blocks(n), ns = alpha_sample_blocks(n, first4k);
-            hipLaunchKernelGGL(k_alphabet_sample, dim3((uint32_t)std::min<uint64_t>(ns, 2ull * (uint32_t)c->cus)),
-                               dim3(kBlock), 0, s, d_text, n, nb, ns, c->alpha);
-            add_bytes(st, SA_K_ALPHABET, alpha_sample_bytes(n, first4k));
-        } else {
-            const uint32_t grid = (uint32_t)std::min<uint64_t>((n + kBlock * 16 - 1) / (kBlock * 16), SA_ALPHA_GRID);
-            hipLaunchKernelGGL(k_alphabet, dim3(grid), dim3(kBlock), 0, s, d_text, n, c->alpha);
-            add_bytes(st, SA_K_ALPHABET, n);
-        }
-        tm.end();
-        SA_HIP(hipGetLastError());
-        SA_HIP(hipMemcpyAsync(h_alpha, c->alpha, 8 * 4, hipMemcpyDeviceToHost, s));
-        SA_HIP(hipMemcpyAsync(h_tail, d_text + (n - tail_n), tail_n, hipMemcpyDeviceToHost, s));
-        SA_HIP(host_sync(s));
-        // the tail's bytes belong to the mask; one the sample missed shows
-        // before any pass that the sample is not the alphabet
-        *complete = true;
-        for (uint32_t t = 0; t < tail_n; ++t) {
-            const uint32_t x = h_tail[t];
-            if (!((h_alpha[x >> 5] >> (x & 31)) & 1u)) *complete = false;
-            h_alpha[x >> 5] |= 1u << (x & 31);
-        }
-        sigma = 0;
-        for (int b = 0; b < 256; ++b) h_code[b] = ((h_alpha[b >> 5] >> (b & 31)) & 1u) ? (uint16_t)(++sigma) : 0;
-        SA_HIP(hipMemcpyAsync(c->code, h_code, 256 * 2, hipMemcpyHostToDevice, s));
-        c->dna = sigma == 4 && h_code['A'] && h_code['C'] && h_code['G'] && h_code['T'];
-        K = choose_chars(sigma, n, opts ? opts->init_chars : 0);
-        // round 1: sort every suffix by its first K symbols -- bucketed (two
-        // global passes + per-window LDS sort) when the text allows it, else the
-        // LSD sort of the packed key
-        // the bucketed round sorts by min_chars symbols (an explicit K as given):
-        // rounding K up to fill radix passes only serves the LSD round, and a
-        // shorter key1 keeps its low bits narrow enough for the fixed-span local
-        // sort and the per-XCD second pass (1 GiB alnum: K 8 -> 7, 16.05 -> 13.59
-        // ms, profiles/r06_h_bench_alnum_k*.log; DNA, ascii127, byte256: the same K)
-        Kb = (opts && opts->init_chars > 0) || sigma <= 1 ? K : min_chars(sigma, n);
-        // (tests: SA_DEBUG_BB17 / _BB18 widen the buckets of a small text; 0 in production)
-        const uint32_t bbf = (c->dbg & SA_DEBUG_BB18) ? 18u : (c->dbg & SA_DEBUG_BB17) ? 17u : 0u;
-        bucketed = plan_bucketed(sigma, n, Kb, r1, c->radix, &bp, 1, (c->dbg & SA_DEBUG_NO_CMP) ? 0 : 1, bbf);
-        if (bucketed && bp.bs.cmp && short_suffix_ties(h_tail, n, tail_n, h_code, sigma, bp.bs.s, bp.bs.R))
-            bucketed = plan_bucketed(sigma, n, Kb, r1, c->radix, &bp, 1, 0, bbf);
-        // a non-power-of-two alphabet one bit short of packed first-pass items
-        // (1 GiB alnum / ascii127: 65 bits) takes the E-only layout when the
-        // text's last K suffixes pad apart (BucketSpec, sa_kernels.h)
-        const bool force_eonly = (c->dbg & SA_DEBUG_EONLY) != 0;
-        if (bucketed && bp.bs.cmp == 1 && ((sigma & (sigma - 1)) != 0 || force_eonly) &&
-            !(c->dbg & SA_DEBUG_NO_EONLY)) {
-            const uint32_t hb = bp.bs.bb - kLoBits;
-            BucketPlan b2;
-            if ((force_eonly || !plan_pk8(bp, hb, c->dbg, true)) && plan_bucketed(sigma, n, Kb, r1, c->radix, &b2, 1, 2, bbf) &&
-                (force_eonly || plan_pk8(b2, hb, c->dbg, true)) &&
-                !short_suffix_ties(h_tail, n, tail_n, h_code, sigma, b2.bs.s, b2.bs.R, b2.K))
-                bp = b2;
-        }
-        return SA_OK;
-    };
-    // The alphabet from a sample (n >= kPadMinN; SA_DEBUG_ALPHA_SAMPLE_SMALL:
-    // any n), kept only when round 1 is then the bucketed one: its first pass
-    // stages every byte of the text and proves the sample (k_split_text,
-    // alpha_bad).  Every other plan (sigma <= 1, no bucket layout, a forced
-    // LSD round) takes the exact pass right here, having paid the sample and
-    // one more host round trip.  A sample the first pass refutes -- a symbol
-    // in none of the sampled blocks -- costs that pass and the second, and the
-    // build starts again with the exact alphabet, once.
-    bool sampled = !(c->dbg & SA_DEBUG_NO_ALPHA_SAMPLE) &&
-                   (n >= kPadMinN || (c->dbg & SA_DEBUG_ALPHA_SAMPLE_SMALL)) && c->radix == 0 && r1 != SA_ROUND1_LSD;
-    bool refuted = false;
-    uint64_t* keys1 = nullptr;
-    uint32_t ksh1 = 0;   // bucketed round 1: keys1 holds every 2^ksh1-th sorted key1
-    uint32_t P = 0;
-    bool fused = false;
-    bool r1_pivot = false;   // round 1 by the pivot split (pivot_round1)
-    uint64_t D = 0, m = 0, G = 0;
-    uint64_t seg1[3] = {0, 0, 0};
-    int r2 = 0;   // round 2 from the local sort's staging (round1_bucketed): 1 gave up, 2 finished the build
-    for (;;) {
-        bool complete = true;
-        rc = plan_round1(sampled, &complete);
-        if (rc) return rc;
-        if (sampled && !(bucketed && complete)) {
-            SA_TRACE("packed: sampled alphabet (sigma=%u) not kept: %s", sigma,
-                     complete ? "round 1 is not bucketed" : "the tail holds another symbol");
-            sampled = false;
-            continue;
-        }
-        c->samples_pending = false;
-        if (!bucketed) break;
-        bool done = false;
-        // (all 256 values in the sample: nothing left to prove)
-        c->alpha_prove = sampled && sigma < 256;
-        c->alpha_refuted = false;
-        rc = round1_bucketed(c, d_text, n, d_sa, bp, full_range(bp, n), s, tm, st, &done, &fused, seg1, &ksh1, true,
-                             true, &r2);
-        c->alpha_prove = false;
-        if (rc) return rc;
-        if (c->alpha_refuted) {
-            SA_TRACE("packed: the first pass met a symbol outside the sampled alphabet, again with the exact one");
-            sampled = false;
-            refuted = true;
-            continue;
-        }
-        bucketed = done;
-        if (done) {
-            keys1 = c->keys[0];
-            P = 2;
-            K = bp.K;
-        }
-        break;
-    }
-    if (st) st->alphabet = refuted ? SA_ALPHABET_REFUTED : sampled ? SA_ALPHABET_SAMPLED : SA_ALPHABET_EXACT;
-    const uint64_t base = (uint64_t)sigma + 1;
-    const Chunking ch = plan_chunks(n);
-    if (!bucketed) {
-        const uint32_t bits1 = key_bits(base, K);
-        SA_TRACE("packed: sigma=%u K=%u bits=%u", sigma, K, bits1);
-        uint64_t top = 1;   // B^(K-1)
-        for (uint32_t t = 1; t < K; ++t) top *= base;
-        if (c->radix == 0) {
-            rc = onesweep_prepare(c, s);
-            if (rc) return rc;
-        }
-        tm.begin(SA_K_PACK);
-        hipLaunchKernelGGL(k_pack_text, dim3(ch.chunks), dim3(kBlock), 0, s, d_text, n, (const uint16_t*)c->code, ch,
-                           base, top, K, c->keys[1], c->hist, c->radix == 0 ? (bits1 + 7) / 8 : 0u, os_ghist(c));
-        tm.end();
-        SA_HIP(hipGetLastError());
-        add_bytes(st, SA_K_PACK, 9 * n);
-        if (c->radix == 0 && !(c->dbg & SA_DEBUG_NO_PIVOT) && n >= (1u << 16)) {
-            rc = pivot_round1(c, n, bits1, d_sa, s, tm, st, &r1_pivot, &D, &m, &G, &P);
-            if (rc) return rc;
-        }
-        if (!r1_pivot) {
-            SrcKeysIota src{c->keys[1]};
-            rc = radix_sort(c, src, 8 * n, ch, bits1, d_sa, c->vals_alt, c->keys[0], c->keys[1], s, tm, st, &keys1,
-                            &P, true);
-            if (rc) return rc;
-        }
-    }
-    if (st) {
-        st->init_chars = (int32_t)K;
-        st->sigma = (int32_t)sigma;
-        st->round1 = bucketed ? SA_ROUND1_BUCKETED : r1_pivot ? SA_ROUND1_PIVOT : SA_ROUND1_LSD;
-    }
-    int uo = 0;
-    bool sparse = false;
-    bool gs_ok[2] = {false, false};   // the set's group starts are in u_gs[set] (pivot rounds' MODE 1)
-    if (r1_pivot) {   // pivot_round1 ran the segments (dense ranks)
-        gs_ok[0] = true;
-    } else if (bucketed && fused) {   // segments came with the local sort (sparse ranks)
-        D = seg1[0];
-        m = seg1[1];
-        G = seg1[2];
-        sparse = true;
-    } else {
-        rc = segments(c, keys1, d_sa, ch, PosIdentity{}, true, &sparse, nullptr, uo, s, tm, st, &D, &m, &G, nullptr,
-                      0, RankMap{}, 0, 0, gs_buf(c, n, uo));
-        if (rc) return rc;
-        gs_ok[uo] = gs_buf(c, n, uo) != nullptr;
-    }
-    // later rounds sort in the two buffers that do not hold the round-1 keys
-    uint64_t* ukb0 = keys1 == c->keys[0] ? c->keys[1] : c->keys[0];
-    uint64_t* ukb1 = c->keys_u;
-    const RankLookup rl{c->rank, c->member, keys1, d_text, (const uint16_t*)c->code, n, base, K,
-                        bucketed ? 1u : 0u, bp.bs, bucketed ? c->segw + kBstartOff : nullptr, d_sa, ksh1};
-    if (st) st->sparse_ranks = sparse ? 1 : 0;
-    // the key1 samples RankLookup::sparse searches, before the first round
-    // that looks a rank up through them (round 1 left them out: SegOut::samples)
-    auto ensure_samples = [&]() -> int {
-        if (!c->samples_pending) return SA_OK;
-        c->samples_pending = false;
-        const uint64_t ns = (n + (1ull << ksh1) - 1) >> ksh1;
-        const uint32_t g = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((ns + kBlock - 1) / kBlock, 8192));
-        tm.begin(SA_K_SORT_U);
-        hipLaunchKernelGGL(k_key1_samples, dim3(g), dim3(kBlock), 0, s, d_text, n, (const uint16_t*)c->code, bp.bs,
-                           (const uint32_t*)d_sa, ksh1, keys1);
-        tm.end();
-        SA_HIP(hipGetLastError());
-        add_bytes(st, SA_K_SORT_U, 12 * ns);
-        return SA_OK;
-    };
-    if (r2 == 0) tm.round_mark();   // (else made before the round-2 kernel)
-    record_round(st, 0.f, D, P, n, K);
-    SA_TRACE("  round 1: D=%llu unsorted=%llu groups=%llu", (unsigned long long)D, (unsigned long long)m,
-             (unsigned long long)G);
-    if (r2 == 2) {
-        // round 2 ordered every group by its next K symbols, no two members
-        // tied: the SA is complete
-        tm.round_mark();
-        D = n;
-        record_round(st, 0.f, D, 1, m, 2 * (uint64_t)K);
-        SA_TRACE("  round h=%u: sorted %llu from the local sort's staging, D=%llu", K, (unsigned long long)m,
-                 (unsigned long long)D);
-        m = 0;
-        G = 0;
-    }
-
-    // doubling rounds over the unsorted set only
-    const uint32_t wr = bit_width(n);   // rank values 0..n
-    for (uint64_t h = K; m > 0; h *= 2) {
-        if (h >= 2 * n) return set_err(SA_E_INTERNAL, "doubling did not converge (h=%llu)", (unsigned long long)h);
-        const uint32_t wg = G > 1 ? bit_width(G - 1) : 0;
-        const uint32_t bits = wg + wr;
-        if (bits > 64) return set_err(SA_E_INTERNAL, "key of %u bits", bits);
-        const Chunking cu = plan_chunks(m);
-        const int ui = uo;
-        uo ^= 1;
-        uint64_t* sorted = nullptr;
-        bool segs_done = false;   // a tied-block pivot round ran its own segments
-        uint64_t Du = 0, m2 = 0, G2 = 0;
-        // the first round after a bucketed round 1 with sparse ranks: the keys'
-        // ranks as key1 of x + K from the text (SrcUKey1) when group id and
-        // key1 + 1 fit 64 bits
-        uint32_t kb1 = 0;
-        if (bucketed && sparse && h == K && !(c->dbg & SA_DEBUG_NO_KEY1_ROUND)) kb1 = key1_bits(bp.bs);
-        const bool key1_round = kb1 > 0 && kb1 + wg <= 64;
-        if (c->radix == 0 && G > 0 && m <= kUsAvg * G) {
-            // small groups on average: sort each group in registers, unless
-            // one of them is larger than kUsLimit (then the radix sort below)
-            if (sparse && !(SA_US_TWO_PHASE && key1_round)) {
-                rc = ensure_samples();
-                if (rc) return rc;
-            }
-            SA_HIP(hipMemsetAsync(c->words + kUsFlagWord, 0, 4, s));
-            const uint32_t grid = (uint32_t)std::min<uint64_t>((m + kBlock - 1) / kBlock, 8192);
-            tm.begin(SA_K_SORT_U);
-#if SA_US_TWO_PHASE
-            // the keys first, one lane per suffix, then each group's lane sorts
-            // them in place (ukb0 is read and written by that lane only)
-            const uint32_t gk = (uint32_t)std::min<uint64_t>((m + kBlock - 1) / kBlock, 65536);
-            if (sparse && key1_round)
-                hipLaunchKernelGGL(k_usort_keys<SrcUKey1>, dim3(gk), dim3(kBlock), 0, s,
-                                   SrcUKey1{c->u_idx[ui], c->u_g[ui], rl, h, kb1}, m, ukb0);
-            else if (sparse)
-                hipLaunchKernelGGL(k_usort_keys<SrcU<true>>, dim3(gk), dim3(kBlock), 0, s,
-                                   SrcU<true>{c->u_idx[ui], c->u_g[ui], rl, h, wr}, m, ukb0);
-            else
-                hipLaunchKernelGGL(k_usort_keys<SrcU<false>>, dim3(gk), dim3(kBlock), 0, s,
-                                   SrcU<false>{c->u_idx[ui], c->u_g[ui], rl, h, wr}, m, ukb0);
-            hipLaunchKernelGGL(k_usort_small<SrcKeys>, dim3(grid), dim3(kBlock), 0, s,
-                               SrcKeys{ukb0, c->u_idx[ui]}, c->u_g[ui], m, ukb0, c->vals_u, c->words + kUsFlagWord);
-#else
-            if (sparse)
-                hipLaunchKernelGGL(k_usort_small<SrcU<true>>, dim3(grid), dim3(kBlock), 0, s,
-                                   SrcU<true>{c->u_idx[ui], c->u_g[ui], rl, h, wr}, c->u_g[ui], m, ukb0, c->vals_u,
-                                   c->words + kUsFlagWord);
-            else
-                hipLaunchKernelGGL(k_usort_small<SrcU<false>>, dim3(grid), dim3(kBlock), 0, s,
-                                   SrcU<false>{c->u_idx[ui], c->u_g[ui], rl, h, wr}, c->u_g[ui], m, ukb0, c->vals_u,
-                                   c->words + kUsFlagWord);
-#endif
-            tm.end();
-            SA_HIP(hipGetLastError());
-            SA_HIP(hipMemcpyAsync(c->host_words + kUsFlagWord, c->words + kUsFlagWord, 4, hipMemcpyDeviceToHost, s));
-            SA_HIP(host_sync(s));
-            add_bytes(st, SA_K_SORT_U, 28 * m);
-            if (c->host_words[kUsFlagWord] == 0) {
-                sorted = ukb0;
-                P = 1;
-            }
-            SA_TRACE("  round h=%llu: per-group register sort %s", (unsigned long long)h,
-                     sorted ? "done" : "found a large group");
-        }
-        if (!sorted && pivot_ok(c, m, G, wr, sparse)) {
-            uint64_t* kbA = ukb0 == c->keys[0] ? c->keys[1] : c->keys[0];   // the round-1 keys: dead with dense ranks
-            bool gsw = false;
-            rc = pivot_round(c, ui, uo, n, m, G, h, wr, ukb0, ukb1, kbA, cu, d_sa, s, tm, st, &sorted, &P,
-                             &segs_done, &Du, &m2, &G2, gs_ok[ui], &gsw);
-            if (rc) return rc;
-            if (segs_done) gs_ok[uo] = gsw;
-        }
-        if (sorted) {
-            rc = SA_OK;
-        } else if (c->radix == 0) {
-            // keys (g, rank[i + h]) once into ukb1 -- the first pass reads them
-            // from there and the second overwrites them -- with the digit totals
-            rc = onesweep_prepare(c, s);
-            if (rc) return rc;
-            const uint32_t Pu = (bits + 7) / 8;
-            const uint32_t grid = (uint32_t)std::min<uint64_t>((m + kBlock - 1) / kBlock, 2048);
-            if (sparse) {
-                rc = ensure_samples();
-                if (rc) return rc;
-            }
-            tm.begin(SA_K_SORT_U);
-            if (sparse)
-                hipLaunchKernelGGL(k_materialize<SrcU<true>>, dim3(grid), dim3(kBlock), 0, s,
-                                   SrcU<true>{c->u_idx[ui], c->u_g[ui], rl, h, wr}, m, Pu, ukb1, os_ghist(c));
-            else
-                hipLaunchKernelGGL(k_materialize<SrcU<false>>, dim3(grid), dim3(kBlock), 0, s,
-                                   SrcU<false>{c->u_idx[ui], c->u_g[ui], rl, h, wr}, m, Pu, ukb1, os_ghist(c));
-            tm.end();
-            SA_HIP(hipGetLastError());
-            add_bytes(st, SA_K_SORT_U, 16 * m);
-            rc = radix_sort(c, SrcKeys{ukb1, c->u_idx[ui]}, 12 * m, cu, bits, c->vals_u, c->vals_alt, ukb0, ukb1, s,
-                            tm, st, &sorted, &P, true, true);
-        } else if (sparse) {
-            rc = ensure_samples();
-            if (rc) return rc;
-            SrcU<true> su{c->u_idx[ui], c->u_g[ui], rl, h, wr};
-            rc = radix_sort(c, su, 12 * m, cu, bits, c->vals_u, c->vals_alt, ukb0, ukb1, s, tm, st, &sorted, &P,
-                            false, true);
-        } else {
-            SrcU<false> su{c->u_idx[ui], c->u_g[ui], rl, h, wr};
-            rc = radix_sort(c, su, 12 * m, cu, bits, c->vals_u, c->vals_alt, ukb0, ukb1, s, tm, st, &sorted, &P,
-                            false, true);
-        }
-        if (rc) return rc;
-        if (!segs_done) {
-            rc = segments(c, sorted, c->vals_u, cu, PosArray{c->u_pos[ui]}, false, nullptr, d_sa, uo, s, tm, st, &Du,
-                          &m2, &G2, nullptr, 0, RankMap{}, 0, 0, gs_buf(c, n, uo));
-            if (rc) return rc;
-            gs_ok[uo] = gs_buf(c, n, uo) != nullptr;
-        }
-        tm.round_mark();
-        D = (n - m) + Du;
-        record_round(st, 0.f, D, P, m, 2 * h);
-        SA_TRACE("  round h=%llu: sorted %llu, D=%llu unsorted=%llu groups=%llu", (unsigned long long)h,
-                 (unsigned long long)m, (unsigned long long)D, (unsigned long long)m2, (unsigned long long)G2);
-        m = m2;
-        G = G2;
-    }
-    if (D != n) return set_err(SA_E_INTERNAL, "finished with %llu groups for n=%llu", (unsigned long long)D,
-                               (unsigned long long)n);
-    return SA_OK;
-}
+// the packed schedule: round 1 by K symbols, then doubling rounds over the
+// unsorted set only
+#include "sa_packed.h"
 
 static int build_device(sa_context* c, const uint8_t* d_text, uint64_t n, uint32_t* d_sa, hipStream_t s,
                         const sa_opts* opts, sa_stats* st) {
@@ -1797,30 +923,27 @@ static int build_device(sa_context* c, const uint8_t* d_text, uint64_t n, uint32
     if (schedule != SA_SCHEDULE_PACKED && schedule != SA_SCHEDULE_REFERENCE)
         return set_err(SA_E_INVALID, "unknown schedule %d", schedule);
     SA_HIP(hipSetDevice(c->device));
-    int rc = ensure_capacity(c, n);
-    if (rc) return rc;
-    Timer tm{c, s, opts && opts->profile, st};
+    SA_TRY(ensure_capacity(c, n));
+    Run r{c, s, opts && opts->profile, st};
     c->radix = opts ? opts->radix : 0;
     set_debug(c, opts);
     if (c->radix != 0 && c->radix != 1) return set_err(SA_E_INVALID, "unknown radix algorithm %d", c->radix);
     SA_HIP(hipMemsetAsync(c->words, 0, 64, s));
     Events ev;
-    rc = ev.make();
-    if (rc) return rc;
+    SA_TRY(ev.make());
     SA_TRACE("build n=%llu schedule=%d", (unsigned long long)n, schedule);
     SA_HIP(hipEventRecord(ev.e[0], s));
     if (n == 1) {
         SA_HIP(hipMemsetAsync(d_sa, 0, 4, s));
     } else if (schedule == SA_SCHEDULE_REFERENCE) {
-        rc = build_reference(c, d_text, n, d_sa, s, st, tm);
+        SA_TRY(build_reference(r, d_text, n, d_sa));
     } else {
-        rc = build_packed(c, d_text, n, d_sa, s, opts, st, tm);
+        SA_TRY(build_packed(r, d_text, n, d_sa, opts));
     }
-    if (rc) return rc;
     SA_HIP(hipEventRecord(ev.e[1], s));
     SA_HIP(hipEventSynchronize(ev.e[1]));
-    tm.flush();
-    tm.round_times();
+    r.flush();
+    r.round_times();
     if (st) st->total_ms = elapsed(ev.e[0], ev.e[1]);
     return SA_OK;
 }
@@ -1830,17 +953,6 @@ static int build_device(sa_context* c, const uint8_t* d_text, uint64_t n, uint32
 // ---------------------------------------------------------------------------
 // O(n) checker (replaces is_valid_suffix_array, manber_myers.c:184-202)
 // ---------------------------------------------------------------------------
-// bin shifts of a checker pass with sub-bins of 2^s2 (plan_perm's shape)
-static PermPlan plan_check(uint64_t n, uint32_t s2, uint32_t b1 = 8) {
-    PermPlan p;
-    const uint32_t lg = bit_width(n > 1 ? n - 1 : 1);
-    p.s2 = s2;
-    p.s1 = std::max<uint32_t>(s2, lg > b1 ? lg - b1 : 0);
-    p.nb1 = (uint32_t)((n + (1ull << p.s1) - 1) >> p.s1);
-    p.nsub = 1u << (p.s1 - p.s2);
-    p.tpb = (uint32_t)(((1ull << p.s1) + kPermBlock * kPermItems - 1) / (kPermBlock * kPermItems));
-    return p;
-}
 
 // level-1 stripes of a permutation (sa_check.h BinStripes): `want` per bin
 // when keys[0] holds the regions with their slack (2^s1 / 128, >= 2048:
@@ -1966,6 +1078,7 @@ static int check_device(sa_context* c, const uint8_t* d_text, uint64_t n, const 
     uint32_t* cur1 = c->hist;
     uint32_t* cur2 = c->hist + kCur2;
     uint64_t* ends = reinterpret_cast<uint64_t*>(c->vals_alt);
+    uint32_t bits = 0;   // the error bits of the last run
     for (uint32_t stripes : {kChkStripes, 1u}) {
         SA_HIP(hipMemsetAsync(err, 0, 4, s));
         uint32_t ran[2] = {1, 1};   // the stripes plan_stripes granted (SA_TRACE)
@@ -2003,13 +1116,32 @@ static int check_device(sa_context* c, const uint8_t* d_text, uint64_t n, const 
             }
         }
         SA_HIP(hipGetLastError());
-        SA_HIP(hipMemcpyAsync(c->host_words + kChkErrWord, err, 4, hipMemcpyDeviceToHost, s));
-        SA_HIP(host_sync(s));
-        SA_TRACE("check (%u stripes asked, %u / %u run in pass A / B): error bits %#x", stripes, ran[0], ran[1],
-                 c->host_words[kChkErrWord]);
-        if (!(c->host_words[kChkErrWord] & 128u)) break;   // else a stripe overflowed: again with one
+        SA_READ(w, read_word(c, kChkErrWord, s));
+        bits = *w;
+        SA_TRACE("check (%u stripes asked, %u / %u run in pass A / B): error bits %#x", stripes, ran[0], ran[1], bits);
+        if (!(bits & 128u)) break;   // else a stripe overflowed: again with one
     }
-    return c->host_words[kChkErrWord] == 0 ? 1 : 0;
+    return bits == 0 ? 1 : 0;
+}
+
+// place_by_permutation with kChkStripes stripes and, when one of them overflowed
+// (only an adversarial SA: it lost pairs), again with one; the error bits stay in
+// words[kPlaceErrWord].  (drop the wait when one stripe was granted.)
+template <class Src, int TAG>
+static int place_striped(sa_context* c, const Src& src, uint64_t n, uint32_t* out, hipStream_t s, const char* what) {
+    for (uint32_t stripes : {kChkStripes, 1u}) {
+        SA_HIP(hipMemsetAsync(c->words + kPlaceErrWord, 0, 4, s));
+        SA_TRY(place_by_permutation<Src, TAG>(c, src, n, out, c->words + kPlaceErrWord, s, stripes));
+        if (stripes == 1) {
+            SA_TRACE("lcp %s (%u stripes asked, %u run)", what, stripes, perm_stripes_run(c, n, stripes));
+            break;
+        }
+        SA_READ(bits, read_word(c, kPlaceErrWord, s));
+        SA_TRACE("lcp %s (%u stripes asked, %u run): error bits %#x", what, stripes, perm_stripes_run(c, n, stripes),
+                 *bits);
+        if (!(*bits & 128u)) break;
+    }
+    return SA_OK;
 }
 
 // ---------------------------------------------------------------------------
@@ -2018,10 +1150,13 @@ static int check_device(sa_context* c, const uint8_t* d_text, uint64_t n, const 
 // their first-mismatch words in vals_alt, pair counts in counts, chunk maxima
 // in hist, the LRS key in words[8..9].
 // ---------------------------------------------------------------------------
+// the longest repeated substring: its length and one position (0, 0: none)
+struct Lrs {
+    uint64_t len = 0, pos = 0;
+};
 static int lcp_device(sa_context* c, const uint8_t* d_text, uint64_t n, const uint32_t* d_sa, uint32_t* d_lcp,
-                      uint64_t* lrs_len, uint64_t* lrs_pos, hipStream_t s) {
-    if (lrs_len) *lrs_len = 0;
-    if (lrs_pos) *lrs_pos = 0;
+                      Lrs* lrs, hipStream_t s) {
+    if (lrs) *lrs = Lrs{};
     if (n == 0) return SA_OK;
     if (!d_text || !d_sa || !d_lcp) return set_err(SA_E_INVALID, "NULL device pointer");
     if ((const void*)d_sa == (const void*)d_lcp) return set_err(SA_E_INVALID, "d_lcp may not alias d_sa");
@@ -2040,20 +1175,7 @@ static int lcp_device(sa_context* c, const uint8_t* d_text, uint64_t n, const ui
     SA_HIP(hipMemsetAsync(best, 0, 8, s));
     // PHI' = PHI + 1 (0: none) by the coalesced permutation (its hole flag for
     // the smallest suffix, which has no predecessor, is expected: words[12])
-    for (uint32_t stripes : {kChkStripes, 1u}) {
-        SA_HIP(hipMemsetAsync(c->words + kPlaceErrWord, 0, 4, s));
-        SA_TRY(place_by_permutation<PhiSrc, 2>(c, PhiSrc{d_sa}, n, phi, c->words + kPlaceErrWord, s, stripes));
-        if (stripes == 1) {
-            SA_TRACE("lcp PHI (%u stripes asked, %u run)", stripes, perm_stripes_run(c, n, stripes));
-            break;
-        }
-        // a level-1 stripe that overflowed (only an adversarial SA) lost pairs
-        SA_HIP(hipMemcpyAsync(c->host_words + kPlaceErrWord, c->words + kPlaceErrWord, 4, hipMemcpyDeviceToHost, s));
-        SA_HIP(host_sync(s));
-        SA_TRACE("lcp PHI (%u stripes asked, %u run): error bits %#x", stripes, perm_stripes_run(c, n, stripes),
-                 c->host_words[kPlaceErrWord]);
-        if (!(c->host_words[kPlaceErrWord] & 128u)) break;
-    }
+    SA_TRY(place_striped<PhiSrc, 2>(c, PhiSrc{d_sa}, n, phi, s, "PHI"));
     hipLaunchKernelGGL(k_plcp_irreducible, dim3(grid), dim3(kBlock), 0, s, d_text, n, (const uint32_t*)phi, v,
                        c->keys[0], c->vals_alt, cnt);
     uint64_t lo = kDirect;
@@ -2077,26 +1199,8 @@ static int lcp_device(sa_context* c, const uint8_t* d_text, uint64_t n, const ui
         hipLaunchKernelGGL(k_lcp_gather, dim3(grid), dim3(kBlock), 0, s, d_sa, n, (const uint32_t*)v, d_lcp, best);
     } else {
         uint32_t* isa1 = c->vals_alt;
-        for (int pass = 0; pass < 2; ++pass) {
-            for (uint32_t stripes : {kChkStripes, 1u}) {
-                SA_HIP(hipMemsetAsync(c->words + kPlaceErrWord, 0, 4, s));
-                if (pass == 0)
-                    SA_TRY(place_by_permutation<IsaSrc, 3>(c, IsaSrc{{d_sa}}, n, isa1, c->words + kPlaceErrWord, s, stripes));
-                else
-                    SA_TRY(place_by_permutation<PlcpSrc, 4>(c, PlcpSrc{isa1, v}, n, d_lcp, c->words + kPlaceErrWord, s,
-                                                            stripes));
-                if (stripes == 1) {
-                    SA_TRACE("lcp %s (%u stripes asked, %u run)", pass ? "PLCP" : "ISA", stripes,
-                             perm_stripes_run(c, n, stripes));
-                    break;
-                }
-                SA_HIP(hipMemcpyAsync(c->host_words + kPlaceErrWord, c->words + kPlaceErrWord, 4, hipMemcpyDeviceToHost, s));
-                SA_HIP(host_sync(s));
-                SA_TRACE("lcp %s (%u stripes asked, %u run): error bits %#x", pass ? "PLCP" : "ISA", stripes,
-                         perm_stripes_run(c, n, stripes), c->host_words[kPlaceErrWord]);
-                if (!(c->host_words[kPlaceErrWord] & 128u)) break;
-            }
-        }
+        SA_TRY(place_striped<IsaSrc, 3>(c, IsaSrc{{d_sa}}, n, isa1, s, "ISA"));
+        SA_TRY(place_striped<PlcpSrc, 4>(c, PlcpSrc{isa1, v}, n, d_lcp, s, "PLCP"));
         hipLaunchKernelGGL(k_lcp_best, dim3(grid), dim3(kBlock), 0, s, (const uint32_t*)d_lcp, n, best);
     }
     SA_HIP(hipGetLastError());
@@ -2117,8 +1221,7 @@ static int lcp_device(sa_context* c, const uint8_t* d_text, uint64_t n, const ui
         const uint64_t r = 0xFFFFFFFFull - (b & 0xFFFFFFFFull);
         uint32_t pos = 0;
         SA_HIP(host_memcpy(&pos, d_sa + r, 4, hipMemcpyDeviceToHost));
-        if (lrs_len) *lrs_len = len;
-        if (lrs_pos) *lrs_pos = pos;
+        if (lrs) *lrs = Lrs{len, pos};
     }
     return SA_OK;
 }
@@ -2267,7 +1370,11 @@ int sa_check_device(sa_context* ctx, const uint8_t* d_text, uint64_t n, const ui
 int sa_lcp_device(sa_context* ctx, const uint8_t* d_text, uint64_t n, const uint32_t* d_sa, uint32_t* d_lcp,
                   uint64_t* lrs_len, uint64_t* lrs_pos, void* stream) {
     if (!ctx) return set_err(SA_E_INVALID, "context is NULL");
-    return lcp_device(ctx, d_text, n, d_sa, d_lcp, lrs_len, lrs_pos, (hipStream_t)stream);
+    Lrs lrs;
+    const int rc = lcp_device(ctx, d_text, n, d_sa, d_lcp, &lrs, (hipStream_t)stream);
+    if (lrs_len) *lrs_len = lrs.len;
+    if (lrs_pos) *lrs_pos = lrs.pos;
+    return rc;
 }
 
 int sa_lcp(const uint8_t* text, uint64_t n, const void* sa, int sa_width, void* lcp_out, uint64_t* lrs_len,
@@ -2655,22 +1762,17 @@ int sa_sort_pairs_device(sa_context* ctx, const uint64_t* d_keys_in, const uint3
         return set_err(SA_E_INVALID, "outputs may not alias inputs");
     hipStream_t s = (hipStream_t)stream;
     SA_HIP(hipSetDevice(ctx->device));
-    int rc = ensure_capacity(ctx, m);
-    if (rc) return rc;
+    SA_TRY(ensure_capacity(ctx, m));
     ctx->radix = 0;
     SA_HIP(hipMemsetAsync(ctx->words, 0, 64, s));
-    Timer tm{ctx, s, false, nullptr};
+    Run r{ctx, s, false, nullptr};
     const Chunking ch = plan_chunks(m);
     SrcKeys src{d_keys_in, d_vals_in};
-    uint64_t* sorted;
-    uint32_t P;
-    rc = radix_sort(ctx, src, 12 * m, ch, bits, d_vals_out, ctx->vals_alt, d_keys_out, ctx->keys[1], s, tm, nullptr,
-                    &sorted, &P);
-    if (rc) return rc;
-    if (sorted != d_keys_out) SA_HIP(hipMemcpyAsync(d_keys_out, sorted, m * 8, hipMemcpyDeviceToDevice, s));
-    SA_HIP(hipMemcpyAsync(ctx->host_words, ctx->words, 20, hipMemcpyDeviceToHost, s));
-    SA_HIP(host_sync(s));
-    if (ctx->host_words[4]) return set_err(SA_E_INTERNAL, "radix look-back did not complete");
+    Sorted so;
+    SA_TRY(radix_sort(r, src, 12 * m, ch, bits, SortBufs{d_vals_out, ctx->vals_alt, d_keys_out, ctx->keys[1]}, &so));
+    if (so.keys != d_keys_out) SA_HIP(hipMemcpyAsync(d_keys_out, so.keys, m * 8, hipMemcpyDeviceToDevice, s));
+    SA_READ(hwd, read_words(ctx, 20, s));
+    if (hwd[kLookbackWord]) return set_err(SA_E_INTERNAL, "radix look-back did not complete");
     return SA_OK;
 }
 
@@ -2691,7 +1793,7 @@ int sa_generate_text_device(uint8_t* d_out, uint64_t n, uint64_t seed, const uin
 int sa_dist_begin(sa_context* ctx, const uint8_t* d_text, uint64_t n, int world, int rank,
                   const uint32_t present[8], uint64_t* d_coarse, void* stream, sa_dist_info* info) {
     if (!ctx || !info) return set_err(SA_E_INVALID, "NULL argument");
-    return dist_begin(ctx, d_text, n, world, rank, present, d_coarse, (hipStream_t)stream, info);
+    return dist_begin(ctx, d_text, n, DistRank{world, rank}, present, d_coarse, (hipStream_t)stream, info);
 }
 
 int sa_dist_cuts(sa_context* ctx, const uint64_t* h_coarse, sa_dist_info* info) {
@@ -2720,14 +1822,16 @@ int sa_dist_plan_cuts(int world, uint64_t n, int bucket_bits, const uint64_t* h_
     std::vector<uint64_t> pre(kCoarse + 1, 0);
     for (uint32_t i = 0; i < kCoarse; ++i) pre[i + 1] = pre[i] + h_coarse[i];
     if (pre[kCoarse] != n) return set_err(SA_E_INVALID, "coarse histogram does not sum to n");
-    return plan_cuts(world, n, (uint32_t)bucket_bits - kCoarseBits, pre.data(), cuts_out, m_max) ? SA_DIST_OK
-                                                                                                  : SA_DIST_UNBALANCED;
+    const CutPlan cp = plan_cuts(world, n, (uint32_t)bucket_bits - kCoarseBits, pre.data(), cuts_out);
+    *m_max = cp.mmax;
+    return cp.ok ? SA_DIST_OK : SA_DIST_UNBALANCED;
 }
 
 int sa_dist_round1(sa_context* ctx, uint32_t* d_sa_local, void* stream, sa_dist_info* info, sa_stats* stats) {
     if (!ctx || !info) return set_err(SA_E_INVALID, "NULL argument");
     if (!ctx->dist) return set_err(SA_E_INVALID, "sa_dist_round1 before sa_dist_begin");
-    return dist_round1(ctx, ctx->dist->text, d_sa_local, (hipStream_t)stream, info, stats);
+    Run r{ctx, (hipStream_t)stream, stats != nullptr, stats};
+    return dist_round1(r, ctx->dist->text, d_sa_local, info);
 }
 
 int sa_dist_req_count(sa_context* ctx, uint64_t h, uint64_t* counts_out, void* stream, sa_dist_info* info) {

@@ -299,6 +299,7 @@ static int inverse_device(sa_context* c, uint64_t n, const uint32_t* d_sa, uint3
     SA_HIP(hipSetDevice(c->device));
     SA_TRY(ensure_capacity(c, n));
     uint32_t* err = c->words + kPlaceErrWord;
+    uint32_t bits = 0;   // the error bits of the last run
     for (uint32_t stripes : {kChkStripes, 1u}) {
         SA_HIP(hipMemsetAsync(err, 0, 4, s));
         SA_TRY(place_by_permutation<IsaSrc, 5, 1>(c, IsaSrc{{d_sa}}, n, d_isa, err, s, stripes));
@@ -309,12 +310,12 @@ static int inverse_device(sa_context* c, uint64_t n, const uint32_t* d_sa, uint3
                            dim3(kBlock), 0, s, (const uint32_t*)c->hist, (const uint32_t*)(c->hist + kCur2), n, p.s1,
                            p.s2, p.nb1, err, bs.st, chk_stride(p));
         SA_HIP(hipGetLastError());
-        SA_HIP(hipMemcpyAsync(c->host_words + kPlaceErrWord, err, 4, hipMemcpyDeviceToHost, s));
-        SA_HIP(host_sync(s));
-        SA_TRACE("inverse (%u stripes asked, %u run): error bits %#x", stripes, bs.st, c->host_words[kPlaceErrWord]);
-        if (!(c->host_words[kPlaceErrWord] & 128u)) break;   // else a stripe overflowed: again with one
+        SA_READ(w, read_word(c, kPlaceErrWord, s));
+        bits = *w;
+        SA_TRACE("inverse (%u stripes asked, %u run): error bits %#x", stripes, bs.st, bits);
+        if (!(bits & 128u)) break;   // else a stripe overflowed: again with one
     }
-    if (c->host_words[kPlaceErrWord]) return set_err(SA_E_INVALID, "SA is not a permutation of [0, n) (error bits %#x)", c->host_words[kPlaceErrWord]);
+    if (bits) return set_err(SA_E_INVALID, "SA is not a permutation of [0, n) (error bits %#x)", bits);
     return SA_OK;
 }
 

@@ -76,7 +76,7 @@ struct DistState {
     uint32_t* owner = nullptr;       // cap_m: owner of each unsorted x's request
     uint32_t* cnt = nullptr;         // [0, W) counts, [W, 2W) cursors, [2W] error flags
     // unsorted set (u_pos / u_idx / u_g[uo] of the context)
-    uint64_t mu = 0, gu = 0;
+    SetTotals set;   // (m suffixes in G groups; D: the heads the last round found)
     int uo = 0;
     std::vector<uint64_t> send;      // requests per owner of the current round
     uint64_t nsend = 0;
@@ -137,8 +137,7 @@ static int ensure_dist_m(sa_context* c, uint64_t m);
 static int dist_reserve(sa_context* c, uint64_t max_n, int world) {
     if (world < 1 || world > kDistMaxWorld) return set_err(SA_E_INVALID, "world %d", world);
     SA_HIP(hipSetDevice(c->device));
-    int rc = ensure_dist_n(c, max_n);
-    if (rc) return rc;
+    SA_TRY(ensure_dist_n(c, max_n));
     const uint64_t w = (uint64_t)world;
     const uint64_t m = std::min<uint64_t>(max_n, max_n / w + max_n / (2 * w) + 65536);
     return ensure_dist_m(c, std::max<uint64_t>(m, 1));
@@ -146,10 +145,8 @@ static int dist_reserve(sa_context* c, uint64_t max_n, int world) {
 
 static int ensure_dist_m(sa_context* c, uint64_t m) {
     DistState* d = dist_of(c);
-    int rc = ensure_capacity(c, m);
-    if (rc) return rc;
-    rc = ensure_u_capacity(c, rec_capacity(m));   // round 1's striped records (sa_round1.h)
-    if (rc) return rc;
+    SA_TRY(ensure_capacity(c, m));
+    SA_TRY(ensure_u_capacity(c, rec_capacity(m)));   // round 1's striped records (sa_round1.h)
     if (d->r1 && d->cap_m >= m) return SA_OK;
     hipFree(d->r1);
     hipFree(d->perm);
@@ -336,8 +333,12 @@ static uint32_t dist_cshift(const DistState& d) { return d.bp.bs.bb - kCoarseBit
 #define SA_DIST_SHORT_K 1
 #endif
 
-static int dist_begin(sa_context* c, const uint8_t* d_text, uint64_t n, int world, int rank,
-                      const uint32_t present[8], uint64_t* d_coarse, hipStream_t s, sa_dist_info* info) {
+struct DistRank {
+    int world, rank;
+};
+static int dist_begin(sa_context* c, const uint8_t* d_text, uint64_t n, DistRank who, const uint32_t present[8],
+                      uint64_t* d_coarse, hipStream_t s, sa_dist_info* info) {
+    const auto [world, rank] = who;
     std::memset(info, 0, sizeof *info);
     if (world < 1 || world > kDistMaxWorld || rank < 0 || rank >= world)
         return set_err(SA_E_INVALID, "rank %d of world %d", rank, world);
@@ -366,9 +367,13 @@ static int dist_begin(sa_context* c, const uint8_t* d_text, uint64_t n, int worl
     info->sigma = (int32_t)sigma;
     BucketPlan bp;
     c->radix = 0;
-    bool planned = plan_bucketed(sigma, n, K, SA_ROUND1_BUCKETED, 0, &bp, world, !(c->dbg & SA_DEBUG_NO_CMP));
+    BucketAsk ask;
+    ask.world = world;
+    ask.cmp = !(c->dbg & SA_DEBUG_NO_CMP);
+    bool planned = plan_bucketed(sigma, n, K, ask, &bp);
+    ask.cmp = 0;
     if (planned && bp.bs.cmp && short_suffix_ties(h_tail, n, tail_n, h_code, sigma, bp.bs.s, bp.bs.R))
-        planned = plan_bucketed(sigma, n, K, SA_ROUND1_BUCKETED, 0, &bp, world, false);
+        planned = plan_bucketed(sigma, n, K, ask, &bp);
     if (!planned) {
         info->status = SA_DIST_UNSUPPORTED;   // one symbol / a key layout that does not fit
         return SA_OK;
@@ -384,8 +389,9 @@ static int dist_begin(sa_context* c, const uint8_t* d_text, uint64_t n, int worl
         unsigned __int128 pk = 1;
         for (uint32_t t = 0; t + 1 < bp.K; ++t) pk *= sigma;
         BucketPlan b2;
+        ask.cmp = bp.bs.cmp != 0;
         if (!plan_pk8(bp, hb_est, c->dbg) && pk >= (unsigned __int128)n * 256u &&
-            plan_bucketed(sigma, n, bp.K - 1, SA_ROUND1_BUCKETED, 0, &b2, world, bp.bs.cmp != 0) &&
+            plan_bucketed(sigma, n, bp.K - 1, ask, &b2) &&
             (!b2.bs.cmp || !short_suffix_ties(h_tail, n, tail_n, h_code, sigma, b2.bs.s, b2.bs.R)) &&
             plan_pk8(b2, hb_est, c->dbg))
             bp = b2;
@@ -424,8 +430,12 @@ static int dist_begin(sa_context* c, const uint8_t* d_text, uint64_t n, int worl
 // cap = 2^18 >> cs coarse buckets (the second pass's local buckets) -- also
 // the ranges still to come: cut[q] >= kCoarse - (W - q) cap.  Returns whether
 // the plan is usable: every range within the cap and the largest within 1.5x
-// of the mean (+ 65536); *mmax = the largest range's suffix count.
-static bool plan_cuts(int W, uint64_t n, uint32_t cs, const uint64_t* pre, uint32_t* cut, uint64_t* mmax) {
+// of the mean (+ 65536); mmax = the largest range's suffix count.
+struct CutPlan {
+    bool ok;
+    uint64_t mmax;
+};
+static CutPlan plan_cuts(int W, uint64_t n, uint32_t cs, const uint64_t* pre, uint32_t* cut) {
     const uint64_t cap = (1ull << 18) >> cs;
     cut[0] = 0;
     cut[W] = kCoarse;
@@ -455,8 +465,7 @@ static bool plan_cuts(int W, uint64_t n, uint32_t cs, const uint64_t* pre, uint3
         mx = std::max(mx, pre[cut[q + 1]] - pre[cut[q]]);
         if ((uint64_t)(cut[q + 1] - cut[q]) > cap) ok = false;
     }
-    *mmax = mx;
-    return ok && mx <= (n / W) + (n / W) / 2 + 65536;
+    return CutPlan{ok && mx <= (n / W) + (n / W) / 2 + 65536, mx};
 }
 
 // h_coarse: the global coarse histogram (sum over ranks; NULL at world 1)
@@ -478,8 +487,7 @@ static int dist_cuts(sa_context* c, const uint64_t* h_coarse, sa_dist_info* info
     }
     const uint32_t cs = dist_cshift(*d);
     d->cut.assign(W + 1, 0);
-    uint64_t mmax = 0;
-    const bool ok = plan_cuts(W, n, cs, pre.data(), d->cut.data(), &mmax);
+    const auto [ok, mmax] = plan_cuts(W, n, cs, pre.data(), d->cut.data());
     const int r = d->rank;
     d->blo = d->cut[r] << cs;
     d->bhi = d->cut[r + 1] << cs;
@@ -496,28 +504,26 @@ static int dist_cuts(sa_context* c, const uint64_t* h_coarse, sa_dist_info* info
     std::vector<uint16_t> tab(kCoarse);
     for (int q = 0; q < W; ++q)
         for (uint32_t i = d->cut[q]; i < d->cut[q + 1]; ++i) tab[i] = (uint16_t)q;
-    int rc = ensure_dist_n(c, n);
-    if (rc) return rc;
-    rc = ensure_dist_m(c, std::max<uint64_t>(d->m, 1));
-    if (rc) return rc;
+    SA_TRY(ensure_dist_n(c, n));
+    SA_TRY(ensure_dist_m(c, std::max<uint64_t>(d->m, 1)));
     SA_HIP(host_memcpy(d->owner_tab, tab.data(), kCoarse * 2, hipMemcpyHostToDevice));
     return SA_OK;
 }
 
-static int dist_round1(sa_context* c, const uint8_t* d_text, uint32_t* d_sa, hipStream_t s, sa_dist_info* info,
-                       sa_stats* st) {
+static int dist_round1(Run& r, const uint8_t* d_text, uint32_t* d_sa, sa_dist_info* info) {
+    sa_context* const c = r.c;
+    const hipStream_t s = r.s;
     DistState* d = c->dist;
     if (!d || !d->planned || d->cut.empty()) return set_err(SA_E_INVALID, "sa_dist_round1 before sa_dist_cuts");
     if (d->m && !d_sa) return set_err(SA_E_INVALID, "NULL SA slice");
-    if (st) {
-        std::memset(st, 0, sizeof *st);
-        st->n_kinds = SA_K_COUNT;
+    if (r.st) {
+        std::memset(r.st, 0, sizeof *r.st);
+        r.st->n_kinds = SA_K_COUNT;
     }
-    Timer tm{c, s, st != nullptr, st};
     c->radix = 0;
     SA_HIP(hipMemsetAsync(c->words, 0, 64, s));
     SA_HIP(hipMemsetAsync(d->cnt, 0, (2 * kDistMaxWorld + 8) * 4, s));
-    d->mu = d->gu = 0;
+    d->set = SetTotals{};
     d->uo = 0;
     info->round1_ok = 1;
     info->heads = 0;
@@ -526,33 +532,24 @@ static int dist_round1(sa_context* c, const uint8_t* d_text, uint32_t* d_sa, hip
         info->groups = 0;
         return SA_OK;
     }
-    BucketRange br;
-    br.blo = d->blo;
-    br.bhi = d->bhi;
-    br.m = d->m;
-    br.sa_off = d->sa_off;
-    br.always_u = true;
-    br.rank = d->crank;
-    br.member = d->gmember;
-    br.prefix = d->gprefix;
-    br.tmp_rank = d->perm;   // free until the first request round
-    bool done = false, fused = false;
-    uint64_t seg[3] = {0, 0, 0};
-    int rc = round1_bucketed(c, d_text, d->n, d_sa, d->bp, br, s, tm, st, &done, &fused, seg, &d->ksh);
+    // (always_u; tmp_rank = perm: free until the first request round)
+    const BucketRange br{d->blo, d->bhi, d->m, d->sa_off, true, d->crank, d->gmember, d->gprefix, d->perm};
+    Bucketed1 b1;
+    int rc = round1_bucketed(r, d_text, d->n, d_sa, d->bp, br, Round1Opts{}, &b1);
+    d->ksh = b1.ksh;
     d->sa = d_sa;
-    tm.flush();
+    r.flush();
     if (rc) return rc;
-    if (!done || !fused) {
+    if (!b1.done || !b1.fused) {
         info->round1_ok = 0;   // a window over the LDS tile: the caller falls back
         return SA_OK;
     }
-    d->mu = seg[1];
-    d->gu = seg[2];
+    d->set = b1.seg;
     d->uo = 0;
     d->rounds = 1;
-    info->heads = seg[0];
-    info->unsorted = seg[1];
-    info->groups = seg[2];
+    info->heads = b1.seg.D;
+    info->unsorted = b1.seg.m;
+    info->groups = b1.seg.G;
     return SA_OK;
 }
 
@@ -562,18 +559,16 @@ static int dist_req_count(sa_context* c, uint64_t h, uint64_t* h_counts, hipStre
     const int W = d->world;
     d->send.assign(W, 0);
     d->nsend = 0;
-    info->unsorted = d->mu;
-    info->groups = d->gu;
-    if (d->mu > 0 && W > 1) {
+    info->unsorted = d->set.m;
+    info->groups = d->set.G;
+    if (d->set.m > 0 && W > 1) {
         SA_HIP(hipMemsetAsync(d->cnt, 0, W * 4, s));
-        const uint32_t grid = (uint32_t)std::min<uint64_t>((d->mu + kBlock - 1) / kBlock, 8192);
-        hipLaunchKernelGGL(k_dist_owner, dim3(grid), dim3(kBlock), 0, s, (const uint32_t*)c->u_idx[d->uo], d->mu, h,
+        const uint32_t grid = (uint32_t)std::min<uint64_t>((d->set.m + kBlock - 1) / kBlock, 8192);
+        hipLaunchKernelGGL(k_dist_owner, dim3(grid), dim3(kBlock), 0, s, (const uint32_t*)c->u_idx[d->uo], d->set.m, h,
                            d->text, d->n, (const uint16_t*)c->code, d->bp.bs, (const uint16_t*)d->owner_tab,
                            dist_cshift(*d), d->owner, d->cnt);
         SA_HIP(hipGetLastError());
-        uint32_t* hc = c->host_words + hw(kHwDistCounts).at;   // pinned scratch (W <= kDistMaxWorld)
-        SA_HIP(hipMemcpyAsync(hc, d->cnt, W * 4, hipMemcpyDeviceToHost, s));
-        SA_HIP(host_sync(s));
+        SA_READ(hc, read_back(c, hw(kHwDistCounts).at, d->cnt, W * 4, s));   // (W <= kDistMaxWorld)
         for (int q = 0; q < W; ++q) {
             d->send[q] = hc[q];
             d->nsend += hc[q];
@@ -602,11 +597,16 @@ static int dist_req_fill(sa_context* c, uint64_t h, uint32_t* d_req, hipStream_t
     if (d->nsend == 0) return SA_OK;
     if (!d_req) return set_err(SA_E_INVALID, "NULL request buffer");
     hipLaunchKernelGGL(k_dist_cursors, dim3(1), dim3(64), 0, s, d->cnt, (uint32_t)d->world);
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((d->mu + kBlock - 1) / kBlock, 8192);
-    hipLaunchKernelGGL(k_dist_fill, dim3(grid), dim3(kBlock), 0, s, (const uint32_t*)c->u_idx[d->uo], d->mu, h,
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((d->set.m + kBlock - 1) / kBlock, 8192);
+    hipLaunchKernelGGL(k_dist_fill, dim3(grid), dim3(kBlock), 0, s, (const uint32_t*)c->u_idx[d->uo], d->set.m, h,
                        (const uint32_t*)d->owner, d->cnt + kDistMaxWorld, d_req, d->perm);
     SA_HIP(hipGetLastError());
     return SA_OK;
+}
+
+static DistLookup dist_lookup(const sa_context* c, const DistState* d) {
+    return DistLookup{d->crank, RankMap{d->gmember, d->gprefix}, c->keys[0], d->sa, d->ksh, c->segw + kBstartOff,
+                      d->text, (const uint16_t*)c->code, d->n, d->bp.bs, d->blo, d->bhi - d->blo, d->sa_off};
 }
 
 static int dist_answer(sa_context* c, const uint32_t* d_req, uint64_t nreq, uint64_t* d_ans, hipStream_t s) {
@@ -614,9 +614,7 @@ static int dist_answer(sa_context* c, const uint32_t* d_req, uint64_t nreq, uint
     if (!d) return set_err(SA_E_INVALID, "no distributed state");
     if (nreq == 0) return SA_OK;
     if (!d_req || !d_ans) return set_err(SA_E_INVALID, "NULL request / answer buffer");
-    const uint32_t nbl = d->bhi - d->blo;
-    const DistLookup L{d->crank, RankMap{d->gmember, d->gprefix}, c->keys[0], d->sa, d->ksh, c->segw + kBstartOff, d->text, (const uint16_t*)c->code,
-                       d->n, d->bp.bs, d->blo, nbl, d->sa_off};
+    const DistLookup L = dist_lookup(c, d);
     const uint32_t grid = (uint32_t)std::min<uint64_t>((nreq + kBlock - 1) / kBlock, 8192);
     hipLaunchKernelGGL(k_dist_answer, dim3(grid), dim3(kBlock), 0, s, d_req, nreq, L, d_ans, d->cnt + 2 * kDistMaxWorld);
     SA_HIP(hipGetLastError());
@@ -629,22 +627,19 @@ static int dist_refine(sa_context* c, uint64_t h, const uint64_t* d_ans, uint32_
     if (!d) return set_err(SA_E_INVALID, "no distributed state");
     info->heads = 0;
     // a request outside this rank's range (k_dist_answer) is a bug
-    uint32_t* hc = c->host_words + hw(kHwDistCounts).at;
-    SA_HIP(hipMemcpyAsync(hc, d->cnt + 2 * kDistMaxWorld, 4, hipMemcpyDeviceToHost, s));
-    SA_HIP(host_sync(s));
-    if (hc[0]) return set_err(SA_E_INTERNAL, "rank request outside this rank's bucket range");
-    if (d->mu == 0) {
+    SA_READ(bad, read_back(c, hw(kHwDistCounts).at, d->cnt + 2 * kDistMaxWorld, 4, s));
+    if (*bad) return set_err(SA_E_INTERNAL, "rank request outside this rank's bucket range");
+    if (d->set.m == 0) {
         info->unsorted = 0;
         info->groups = 0;
         return SA_OK;
     }
     if (d->nsend && !d_ans) return set_err(SA_E_INVALID, "NULL answer buffer");
     if (h >= 2 * d->n) return set_err(SA_E_INTERNAL, "doubling did not converge (h=%llu)", (unsigned long long)h);
-    Timer tm{c, s, false, nullptr};
-    const uint64_t m = d->mu, G = d->gu;
+    Run r{c, s, false, nullptr};
+    const uint64_t m = d->set.m, G = d->set.G;
     if (d->world == 1) {   // every look-up is local: no request / answer exchange
-        const DistLookup L{d->crank, RankMap{d->gmember, d->gprefix}, c->keys[0], d->sa, d->ksh, c->segw + kBstartOff, d->text, (const uint16_t*)c->code,
-                           d->n, d->bp.bs, d->blo, d->bhi - d->blo, d->sa_off};
+        const DistLookup L = dist_lookup(c, d);
         const uint32_t grid = (uint32_t)std::min<uint64_t>((m + kBlock - 1) / kBlock, 8192);
         hipLaunchKernelGGL(k_dist_r1_local, dim3(grid), dim3(kBlock), 0, s, (const uint32_t*)c->u_idx[d->uo], m, h, L,
                            d->r1, d->cnt + 2 * kDistMaxWorld);
@@ -667,43 +662,34 @@ static int dist_refine(sa_context* c, uint64_t h, const uint64_t* d_ans, uint32_
     const SrcUArr src{c->u_idx[ui], c->u_g[ui], d->r1, wr};
     uint64_t* ukb0 = c->keys[1];   // keys[0] holds the round-1 keys (look-ups)
     uint64_t* ukb1 = c->keys_u;
-    uint64_t* sorted = nullptr;
-    uint32_t P = 0;
+    const SortBufs bufs{c->vals_u, c->vals_alt, ukb0, ukb1};
+    Sorted so;
     if (G > 0 && m <= kUsAvg * G) {
-        SA_HIP(hipMemsetAsync(c->words + kUsFlagWord, 0, 4, s));
-        const uint32_t grid = (uint32_t)std::min<uint64_t>((m + kBlock - 1) / kBlock, 8192);
-        hipLaunchKernelGGL(k_usort_small<SrcUArr>, dim3(grid), dim3(kBlock), 0, s, src, c->u_g[ui], m, ukb0,
-                           c->vals_u, c->words + kUsFlagWord);
-        SA_HIP(hipGetLastError());
-        SA_HIP(hipMemcpyAsync(c->host_words + kUsFlagWord, c->words + kUsFlagWord, 4, hipMemcpyDeviceToHost, s));
-        SA_HIP(host_sync(s));
-        if (c->host_words[kUsFlagWord] == 0) sorted = ukb0;
+        bool ok = false;
+        SA_TRY(usort_try(r, [&] {
+            const uint32_t grid = (uint32_t)std::min<uint64_t>((m + kBlock - 1) / kBlock, 8192);
+            hipLaunchKernelGGL(k_usort_small<SrcUArr>, dim3(grid), dim3(kBlock), 0, s, src, c->u_g[ui], m, ukb0,
+                               c->vals_u, c->words + kUsFlagWord);
+        }, &ok));
+        if (ok) so.keys = ukb0;
     }
-    if (!sorted) {
-        int rc = onesweep_prepare(c, s);
-        if (rc) return rc;
-        const uint32_t Pu = (bits + 7) / 8;
-        const uint32_t grid = (uint32_t)std::min<uint64_t>((m + kBlock - 1) / kBlock, 2048);
-        hipLaunchKernelGGL(k_materialize<SrcUArr>, dim3(grid), dim3(kBlock), 0, s, src, m, Pu, ukb1, os_ghist(c));
-        SA_HIP(hipGetLastError());
-        rc = radix_sort(c, SrcKeys{ukb1, c->u_idx[ui]}, 12 * m, plan_chunks(m), bits, c->vals_u, c->vals_alt, ukb0,
-                        ukb1, s, tm, nullptr, &sorted, &P, true, true);
-        if (rc) return rc;
-    }
-    uint64_t Du = 0, m2 = 0, G2 = 0;
-    int rc = segments(c, sorted, c->vals_u, plan_chunks(m), PosArray{c->u_pos[ui]}, false, nullptr, d_sa, uo, s, tm,
-                      nullptr, &Du, &m2, &G2, d->crank, d->sa_off, RankMap{d->gmember, d->gprefix});
-    if (rc) return rc;
+    if (!so.keys) SA_TRY(usort_radix(r, src, c->u_idx[ui], m, bits, bufs, [] { return (int)SA_OK; }, &so));
+    SegDest dest;
+    dest.rank_arr = d->crank;
+    dest.rank_off = d->sa_off;
+    dest.rm = RankMap{d->gmember, d->gprefix};
+    SegResult sr;
+    SA_TRY(segments(r, SegSrc{so.keys, c->vals_u, plan_chunks(m)}, PosArray{c->u_pos[ui]}, false, d_sa, uo, &sr, dest));
     if (d->world == 1) {   // the local look-ups' range check (segments() synchronised the stream)
+        uint32_t* hc = c->host_words + hw(kHwDistCounts).at;
         SA_HIP(host_memcpy(hc, d->cnt + 2 * kDistMaxWorld, 4, hipMemcpyDeviceToHost));
         if (hc[0]) return set_err(SA_E_INTERNAL, "rank look-up outside the bucket range");
     }
-    d->mu = m2;
-    d->gu = G2;
+    d->set = sr.t;
     d->uo = uo;
     d->rounds++;
-    info->heads = Du;
-    info->unsorted = m2;
-    info->groups = G2;
+    info->heads = sr.t.D;
+    info->unsorted = sr.t.m;
+    info->groups = sr.t.G;
     return SA_OK;
 }

@@ -354,8 +354,11 @@ static int lcp_host(const uint8_t* text, uint64_t n, const void* sa, int sa_widt
     const int valid = check_device(c, d_text.as<uint8_t>(), n, d_sa.as<uint32_t>(), nullptr);
     if (valid == 0) return set_err(SA_E_INVALID, "not a valid suffix array of the text");
     if (valid != 1) return valid;
-    SA_TRY(lcp_device(c, d_text.as<uint8_t>(), n, d_sa.as<uint32_t>(), d_lcp.as<uint32_t>(), lrs_len, lrs_pos,
-                      nullptr));
+    Lrs lrs;
+    const int rc = lcp_device(c, d_text.as<uint8_t>(), n, d_sa.as<uint32_t>(), d_lcp.as<uint32_t>(), &lrs, nullptr);
+    if (lrs_len) *lrs_len = lrs.len;
+    if (lrs_pos) *lrs_pos = lrs.pos;
+    if (rc) return rc;
     return copy_d2h(lcp_out, d_lcp.as<uint32_t>(), n, sa_width, nullptr);
 }
 

@@ -590,7 +590,7 @@ static int lce_positions_host(bool order, const uint8_t* text, uint64_t n, const
     const int ok = check_device(c, d_text.as<uint8_t>(), n, d_sa.as<uint32_t>(), nullptr);
     if (ok == 0) return set_err(SA_E_INVALID, "not a valid suffix array of the text");
     if (ok != 1) return ok;
-    SA_TRY(lcp_device(c, d_text.as<uint8_t>(), n, d_sa.as<uint32_t>(), d_lcp.as<uint32_t>(), nullptr, nullptr, nullptr));
+    SA_TRY(lcp_device(c, d_text.as<uint8_t>(), n, d_sa.as<uint32_t>(), d_lcp.as<uint32_t>(), nullptr, nullptr));
     SA_TRY(inverse_device(c, n, d_sa.as<uint32_t>(), d_isa.as<uint32_t>(), nullptr));
     SA_TRY(lce_build_device(n, d_lcp.as<uint32_t>(), d_idx.p, ib, nullptr));
     const uint32_t* dq = d_q.as<uint32_t>();

@@ -36,7 +36,11 @@ struct HostRegion {
     bool wide;          // read through a uint64_t*
 };
 constexpr uint32_t kHostWords = 4096;          // sa_context_create allocates these
+constexpr int kDWord = 0;                      // words[]: distinct keys (group heads) of the set just segmented
+constexpr int kMWord = 1;                      // words[]: its suffixes left unsorted
+constexpr int kGWord = 2;                      // words[]: their groups
 constexpr int kChkErrWord = 3;                 // words[]: the checker's error bits
+constexpr int kLookbackWord = 4;               // words[]: a radix pass's look-back did not complete
 constexpr int kPadOverWord = 11;               // words[]: a digit outgrew its padded segment
 constexpr int kPlaceErrWord = 12;              // words[]: place_by_permutation's error bits (LCP, inverse SA)
 

@@ -623,7 +623,7 @@ static int lpf_device(sa_context* c, const uint8_t* d_text, uint64_t n, const ui
     LocBuf own_lcp;
     if (!d_lcp) {
         SA_TRY(own_lcp.alloc(align_up(n, 64) * 4, s));
-        SA_TRY(lcp_device(c, d_text, n, d_sa, (uint32_t*)own_lcp.p, nullptr, nullptr, s));
+        SA_TRY(lcp_device(c, d_text, n, d_sa, (uint32_t*)own_lcp.p, nullptr, s));
         d_lcp = (const uint32_t*)own_lcp.p;
     }
     LpfLevels g;

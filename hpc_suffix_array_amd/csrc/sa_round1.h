@@ -124,8 +124,12 @@ struct BucketPlan {
 // bb_min (one GPU; tests: SA_DEBUG_BB17 / _BB18): bucket bits the plan takes when the size
 // alone gives fewer (17 or 18; 0: the size decides) -- the second pass's 9-
 // and 10-bit digits at sizes a CPU oracle sorts.  Never lowers bb.
-static bool plan_bucketed(uint32_t sigma, uint64_t n, uint32_t K, int round1, int radix, BucketPlan* p,
-                          int world = 1, int cmp = 0, uint32_t bb_min = 0) {
+struct BucketAsk {
+    int round1 = SA_ROUND1_BUCKETED, radix = 0, world = 1, cmp = 0;
+    uint32_t bb_min = 0;
+};
+static bool plan_bucketed(uint32_t sigma, uint64_t n, uint32_t K, const BucketAsk& ask, BucketPlan* p) {
+    const auto [round1, radix, world, cmp, bb_min] = ask;
     if (round1 == SA_ROUND1_LSD || radix != 0 || sigma < 2 || n < 2) return false;
     if (round1 == SA_ROUND1_AUTO && n < kBucketMinN) return false;
     // bucket bits: windows of about n / 2^bb suffixes must fit the
@@ -270,31 +274,38 @@ static uint32_t range_hb(uint32_t nb) {
     return std::max<uint32_t>(7u, w > kLoBits ? w - kLoBits : 0u);
 }
 
-// *done: the SA and keys[0] hold the sorted first round (keys[0]: the key1
-// of every 2^*ksh-th SA position when *fused, else every key1).  *fused: the
+// allow_pad / allow_xq: padded (or striped) first-pass segments and the second
+// pass's per-XCD queues may be taken (cleared for the re-run after an overflow).
+// want_round2 (one GPU): round 2 is tried from the local sort's staging
+// (k_round2_windows) behind the round-1 boundary mark.
+struct Round1Opts {
+    bool allow_pad = true, allow_xq = true, want_round2 = false;
+};
+// done: the SA and keys[0] hold the sorted first round (keys[0]: the key1
+// of every 2^ksh-th SA position when fused, else every key1).  fused: the
 // round-1 segments were produced with it (few unsorted suffixes): rank[] for
-// the unsorted set only (member bitmap), the unsorted set compacted in
-// u_pos/u_idx/u_g[0], and seg = {D, m, G}; otherwise the caller runs
-// segments() on keys[0].
-// round2 (non-null: the caller can take it; one GPU): round 2 is tried
-// straight from the local sort's staging (k_round2_windows) behind the
-// round-1 boundary mark.  *round2 = 2: it finished the build (the SA is
-// complete; the set was not compacted); 1: it gave up and the set was
-// compacted as usual, the mark stays; 0: not run, or round 1 goes on in the
-// caller (the mark withdrawn).
-static int round1_bucketed(sa_context* c, const uint8_t* d_text, uint64_t n, uint32_t* d_sa, const BucketPlan& bp,
-                           const BucketRange& br_, hipStream_t s, Timer& tm, sa_stats* st, bool* done, bool* fused,
-                           uint64_t seg[3], uint32_t* ksh, bool allow_pad = true, bool allow_xq = true,
-                           int* round2 = nullptr) {
-    *done = false;
-    *fused = false;
-    *ksh = 0;
-    if (round2) *round2 = 0;
+// the unsorted set only (member bitmap), the set compacted in u_pos/u_idx/u_g[0],
+// seg = its totals; otherwise the caller runs segments() on keys[0].
+// round2 = 2: round 2 finished the build (the SA is complete; the set was
+// not compacted); 1: it gave up and the set was compacted as usual, the mark
+// stays; 0: not run, or round 1 goes on in the caller (the mark withdrawn).
+struct Bucketed1 {
+    bool done = false, fused = false;
+    SetTotals seg;
+    uint32_t ksh = 0;
+    int round2 = 0;
+};
+static int round1_bucketed(Run& r, const uint8_t* d_text, uint64_t n, uint32_t* d_sa, const BucketPlan& bp,
+                           const BucketRange& br_, Round1Opts o, Bucketed1* out) {
+    sa_context* const c = r.c;
+    const hipStream_t s = r.s;
+    sa_stats* const st = r.st;
+    const bool allow_pad = o.allow_pad, allow_xq = o.allow_xq;
+    *out = Bucketed1{};
     const uint64_t m = br_.m;   // suffixes of this range (= n on one GPU)
     const uint32_t blo = br_.blo, bhi = br_.bhi;
     if (bhi <= blo || bhi - blo > (1u << 18)) return set_err(SA_E_INTERNAL, "bucket range [%u, %u)", blo, bhi);
-    int rc = onesweep_prepare(c, s);
-    if (rc) return rc;
+    SA_TRY(onesweep_prepare(c, s));
     // [0..2] D, m, G of the fused segments, [5] largest window, [6] local-sort
     // flags, [7] windows, [8] a byte outside the sampled alphabet, [10] skewed
     // windows
@@ -339,7 +350,7 @@ static int round1_bucketed(sa_context* c, const uint8_t* d_text, uint64_t n, uin
     uint32_t* const pstart = os_base(c) + kPadStartOff;   // kLoRadix + 1 padded segment starts
     uint32_t* const dlo = os_base(c) + kPadDenseOff;      // kLoRadix dense segment starts
     if (st) st->round1_segments = padded ? 1 : striped ? 3 : 0;
-    tm.begin(SA_K_PACK);
+    r.begin(SA_K_PACK);
     if (padded) {
         const bool pow2 = (bp.bs.sigma & (bp.bs.sigma - 1)) == 0;
         const uint32_t g = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(((n >> ssh) + kBlock - 1) / kBlock,
@@ -384,13 +395,11 @@ static int round1_bucketed(sa_context* c, const uint8_t* d_text, uint64_t n, uin
             else if (pow2) SA_HIST_G(rgrid, true, 3, rcur);
             else SA_HIST_G(rgrid, false, 3, rcur);
             // an overflowed stripe dropped records: stop before any pass reads them
-            SA_HIP(hipMemcpyAsync(c->host_words + kPadOverWord, c->words + kPadOverWord, 4, hipMemcpyDeviceToHost, s));
-            SA_HIP(host_sync(s));
-            if (c->host_words[kPadOverWord]) {
+            SA_READ(over, read_word(c, kPadOverWord, s));
+            if (*over) {
                 SA_TRACE("  bucketed round 1: a record stripe overflowed, again with the counting scan");
-                tm.end();
-                const int rc = round1_bucketed(c, d_text, n, d_sa, bp, br_, s, tm, st, done, fused, seg, ksh, false,
-                                               allow_xq, round2);
+                r.end();
+                const int rc = round1_bucketed(r, d_text, n, d_sa, bp, br_, Round1Opts{false, allow_xq, o.want_round2}, out);
                 if (st) st->round1_segments = 4;
                 return rc;
             }
@@ -410,8 +419,8 @@ static int round1_bucketed(sa_context* c, const uint8_t* d_text, uint64_t n, uin
 #undef SA_HIST_G
 #undef SA_HIST_ID_G
     }
-    tm.end();
-    add_bytes(st, SA_K_PACK, padded ? (n >> ssh) * 64 : n + (striped ? 12 * m : listed ? n + 12 * m : 0));
+    r.end();
+    r.bytes(SA_K_PACK, padded ? (n >> ssh) * 64 : n + (striped ? 12 * m : listed ? n + 12 * m : 0));
     // second-pass digit bits (7..10): bb - kLoBits on one GPU
     const uint32_t hb = (blo == 0 && bhi == (1u << bp.bs.bb)) ? bp.bs.bb - kLoBits : range_hb(bhi - blo);
     if (hb < 7 || hb > 10) return set_err(SA_E_INTERNAL, "second bucket pass of %u bits", hb);
@@ -490,14 +499,14 @@ static int round1_bucketed(sa_context* c, const uint8_t* d_text, uint64_t n, uin
     uint32_t* const cursor_sum = stripes > 1 ? c->hist + kMaxStripes * kLoRadix : cursor;
     if (stripes > 1) SA_HIP(hipMemsetAsync(cursor, 0, (size_t)stripes * kLoRadix * 4, s));
     if (!padded) {
-        tm.begin(SA_K_SCAN);
+        r.begin(SA_K_SCAN);
         hipLaunchKernelGGL(k_digit_base_wide, dim3(1), dim3(1024), 0, s, (const uint32_t*)g_lo, kLoRadix, os_base(c));
-        tm.end();
+        r.end();
     }
     // two passes over the bucket: its low kLoBits (any order within a
     // digit), then its high hb bits, keeping the low digit's order (text
     // order -> bucket order; sa_split.h)
-    tm.begin(SA_K_SCATTER_FIRST);
+    r.begin(SA_K_SCATTER_FIRST);
     {
         // 12288-position tiles (8192: 5.7 ms, measured on the same box)
         constexpr int kItemsA = SA_ITEMS_A;
@@ -572,9 +581,9 @@ static int round1_bucketed(sa_context* c, const uint8_t* d_text, uint64_t n, uin
         }
 #undef SA_TEXT_PASS
     }
-    tm.end();
-    add_bytes(st, SA_K_SCATTER_FIRST, listed ? (pk8 ? 20 : 24) * m : n + (pk8 ? 8 : 12) * m);
-    tm.begin(SA_K_SCAN);   // the second pass's digit totals came from the first
+    r.end();
+    r.bytes(SA_K_SCATTER_FIRST, listed ? (pk8 ? 20 : 24) * m : n + (pk8 ? 8 : 12) * m);
+    r.begin(SA_K_SCAN);   // the second pass's digit totals came from the first
     hipLaunchKernelGGL(k_digit_base_wide, dim3(1), dim3(1024), 0, s, (const uint32_t*)g_hi, 1u << hb,
                        os_base(c) + kLoRadix);
     if (xq)   // the digits' sub-regions of each queue's region
@@ -586,8 +595,8 @@ static int round1_bucketed(sa_context* c, const uint8_t* d_text, uint64_t n, uin
             hipLaunchKernelGGL(k_sum_rows, dim3(1), dim3(kLoRadix), 0, s, (const uint32_t*)cursor, stripes, cursor_sum);
         hipLaunchKernelGGL(k_digit_base_wide, dim3(1), dim3(1024), 0, s, (const uint32_t*)cursor_sum, kLoRadix, dlo);
     }
-    tm.end();
-    tm.begin(SA_K_SCATTER_KEYS);
+    r.end();
+    r.begin(SA_K_SCATTER_KEYS);
     {
         // 12288-pair units cut at the first pass's digit boundaries, places
         // claimed per (low digit, high digit) by atomic cursors (sa_split.h)
@@ -662,14 +671,14 @@ static int round1_bucketed(sa_context* c, const uint8_t* d_text, uint64_t n, uin
         }
 #undef SA_BSTARTS
     }
-    tm.end();
-    add_bytes(st, SA_K_SCATTER_KEYS, (pk8 ? 16 : 20) * m);
+    r.end();
+    r.bytes(SA_K_SCATTER_KEYS, (pk8 ? 16 : 20) * m);
     SA_HIP(hipGetLastError());
     // windows of whole buckets; ws lives in vals_alt (free again; nw + 1 <= m)
     const uint64_t nw = (m + kWinStride - 1) / kWinStride;
     uint32_t* ws = c->vals_alt;
     uint32_t* list = c->vals_alt + nw + 1;   // non-empty windows (2 nw + 1 <= n)
-    tm.begin(SA_K_WINDOWS);
+    r.begin(SA_K_WINDOWS);
     {
         const uint32_t g1 = (uint32_t)std::min<uint64_t>((nw + kBlock) / kBlock, 8192);
         hipLaunchKernelGGL(k_window_starts_tab, dim3(g1), dim3(kBlock), 0, s, (const uint32_t*)(c->segw + kBstartOff),
@@ -677,8 +686,8 @@ static int round1_bucketed(sa_context* c, const uint8_t* d_text, uint64_t n, uin
         const uint32_t g2 = (uint32_t)std::min<uint64_t>((nw + kBlock - 1) / kBlock, 1024);
         hipLaunchKernelGGL(k_window_list, dim3(g2), dim3(kBlock), 0, s, (const uint32_t*)ws, nw, list, c->words);
     }
-    tm.end();
-    add_bytes(st, SA_K_WINDOWS, 8 * nw);
+    r.end();
+    r.bytes(SA_K_WINDOWS, 8 * nw);
     SA_HIP(hipGetLastError());
     SA_HIP(hipMemcpyAsync(c->host_words, c->words, 48, hipMemcpyDeviceToHost, s));
     // windows with clustered keys, then per-window U / U-group counts (scanned
@@ -703,18 +712,16 @@ static int round1_bucketed(sa_context* c, const uint8_t* d_text, uint64_t n, uin
         c->alpha_refuted = true;
         return SA_OK;
     }
-    if (c->host_words[4]) return set_err(SA_E_INTERNAL, "radix look-back did not complete");
+    if (c->host_words[kLookbackWord]) return set_err(SA_E_INTERNAL, "radix look-back did not complete");
     if (padded && c->host_words[kPadOverWord]) {   // a digit outgrew its sampled segment: exact totals
         SA_TRACE("  bucketed round 1: padded segment overflow, again with exact digit totals");
-        const int rc = round1_bucketed(c, d_text, n, d_sa, bp, br_, s, tm, st, done, fused, seg, ksh, false, allow_xq,
-                                       round2);
+        const int rc = round1_bucketed(r, d_text, n, d_sa, bp, br_, Round1Opts{false, allow_xq, o.want_round2}, out);
         if (st) st->round1_segments = 2;
         return rc;
     }
     if (xq && c->host_words[9]) {   // a queue's digit outgrew its sub-region: one region
         SA_TRACE("  bucketed round 1: second-pass queue overflow, again with one region");
-        return round1_bucketed(c, d_text, n, d_sa, bp, br_, s, tm, st, done, fused, seg, ksh, allow_pad, false,
-                               round2);
+        return round1_bucketed(r, d_text, n, d_sa, bp, br_, Round1Opts{allow_pad, false, o.want_round2}, out);
     }
     if (st) st->largest_window = (int32_t)std::min<uint32_t>(c->host_words[5], INT32_MAX);
     if (c->host_words[5] > (uint32_t)kBsCap) {
@@ -828,10 +835,10 @@ static int round1_bucketed(sa_context* c, const uint8_t* d_text, uint64_t n, uin
                            wide_in, br, (const uint32_t*)ws, (const uint32_t*)skew, c->words, bp.ib,
                            c->keys[0], d_sa, o);
     };
-    tm.begin(SA_K_LOCAL_SORT);
+    r.begin(SA_K_LOCAL_SORT);
     local_sort(so);
-    tm.end();
-    add_bytes(st, SA_K_LOCAL_SORT, 12 * m + (so.samples ? (m >> kKeySample) * 8 : 0));
+    r.end();
+    r.bytes(SA_K_LOCAL_SORT, 12 * m + (so.samples ? (m >> kKeySample) * 8 : 0));
     SA_HIP(hipGetLastError());
     // the unsorted set, in SA order, compacted (a round that turns out dense,
     // or falls back, ignores it: segments() writes the set again)
@@ -865,76 +872,73 @@ static int round1_bucketed(sa_context* c, const uint8_t* d_text, uint64_t n, uin
     // is compacted only when that gives up (cnt_u is still unscanned then).
     // Otherwise the set is compacted before the counts are read back (its
     // launches overlap that round trip).
-    const bool try_r2 = round2 && so.rank && !br_.always_u && !so.tmp_rank && br_.sa_off == 0 &&
+    const bool try_r2 = o.want_round2 && so.rank && !br_.always_u && !so.tmp_rank && br_.sa_off == 0 &&
                         !(c->dbg & (SA_DEBUG_NO_KEY1_ROUND | SA_DEBUG_NO_ROUND2_FUSED)) && key1_bits(bp.bs) <= 64;
     if (try_r2) {
-        tm.round_mark();
-        tm.begin(SA_K_SORT_U);
+        r.round_mark();
+        r.begin(SA_K_SORT_U);
         const uint64_t per = (uint64_t)kWaves * kR2Batch;
         const uint32_t g = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((c->host_words[7] + per - 1) / per, 65536));
         hipLaunchKernelGGL(k_round2_windows, dim3(g), dim3(kBlock), 0, s, (const uint32_t*)list,
                            (const uint32_t*)c->words, (const uint32_t*)ws, (const uint32_t*)cnt_u,
                            (const uint32_t*)so.tmp_pos, (const uint32_t*)so.tmp_idx, (const uint32_t*)so.tmp_g, d_text, n,
                            (const uint16_t*)c->code, bp.bs, m, d_sa, c->words + kUsFlagWord);
-        tm.end();
+        r.end();
     } else {
-        tm.begin(SA_K_SEG_WRITE);
+        r.begin(SA_K_SEG_WRITE);
         gather_u();
-        tm.end();
+        r.end();
     }
     SA_HIP(hipGetLastError());
-    SA_HIP(hipMemcpyAsync(c->host_words, c->words, 64, hipMemcpyDeviceToHost, s));
-    SA_HIP(host_sync(s));
+    SA_READ(hwd, read_words(c, 64, s));
     if (st) {   // where the first launch sent the windows (the dense re-run below recounts words 13-15)
         const uint32_t wv[4] = {c->host_words[7], c->host_words[kHdrWord], c->host_words[kRetryWord], c->host_words[10]};
         for (int t = 0; t < 4; ++t) st->round1_windows[t] = (int32_t)std::min<uint32_t>(wv[t], INT32_MAX);
     }
     if (c->host_words[6]) {
         SA_TRACE("  bucketed round 1: local sort flags %u, full sort instead", c->host_words[6]);
-        if (try_r2) tm.round_unmark();
+        if (try_r2) r.round_unmark();
         return SA_OK;
     }
-    seg[0] = c->host_words[0];
-    seg[1] = c->host_words[1];
-    seg[2] = c->host_words[2];
-    add_bytes(st, SA_K_LOCAL_SORT, seg[1] * 28);   // unsorted set: rank, member bit, 3 tmp words
-    const bool sparse = br_.always_u || seg[1] <= n / kSparseDiv;
+    const SetTotals seg = out->seg = totals_of(hwd);
+    r.bytes(SA_K_LOCAL_SORT, seg.m * 28);   // unsorted set: rank, member bit, 3 tmp words
+    const bool sparse = br_.always_u || seg.m <= n / kSparseDiv;
     if (try_r2) {
-        add_bytes(st, SA_K_SORT_U, seg[1] * 28);   // 3 tmp words, the key's text words, the SA entry
+        r.bytes(SA_K_SORT_U, seg.m * 28);   // 3 tmp words, the key's text words, the SA entry
         if (!sparse) {
-            tm.round_unmark();   // round 1 goes on (the caller's segments())
+            r.round_unmark();   // round 1 goes on (the caller's segments())
         } else if (c->host_words[kUsFlagWord] == 0) {
             SA_TRACE("  bucketed round 1: round 2 finished from the staging (%llu members)",
-                     (unsigned long long)seg[1]);
-            *round2 = 2;
+                     (unsigned long long)seg.m);
+            out->round2 = 2;
         } else {
             SA_TRACE("  bucketed round 1: round 2 from the staging gave up, the set compacted");
-            *round2 = 1;
-            tm.begin(SA_K_SEG_WRITE);
+            out->round2 = 1;
+            r.begin(SA_K_SEG_WRITE);
             gather_u();
-            tm.end();
+            r.end();
             SA_HIP(hipGetLastError());
         }
     }
-    if (!try_r2 || *round2 == 1) add_bytes(st, SA_K_SEG_WRITE, 8 * (2 * nw + 2) + seg[1] * 24);
+    if (!try_r2 || out->round2 == 1) r.bytes(SA_K_SEG_WRITE, 8 * (2 * nw + 2) + seg.m * 24);
     if (!sparse) {
         // dense ranks follow (segments() over every key1): the same sort
         // again, writing every key1 and nothing of the unsorted set
         SegOut full{};
         full.ksh = 0;
         SA_HIP(hipMemsetAsync(c->words + 10, 0, 4, s));   // the skewed-window list is rebuilt
-        tm.begin(SA_K_LOCAL_SORT);
+        r.begin(SA_K_LOCAL_SORT);
         local_sort(full);
-        tm.end();
-        add_bytes(st, SA_K_LOCAL_SORT, 20 * m);
+        r.end();
+        r.bytes(SA_K_LOCAL_SORT, 20 * m);
         SA_HIP(hipGetLastError());
     } else {
-        *ksh = kKeySample;
-        *fused = true;
+        out->ksh = kKeySample;
+        out->fused = true;
         c->samples_pending = so.samples == 0u;
     }
     SA_TRACE("  bucketed round 1: s=%u R=%u rb=%u cmp=%u pk8=%d windows=%u (skewed %u) largest=%u", bp.bs.s, bp.bs.R,
              bp.bs.rb, bp.bs.cmp, pk8 ? 1 : 0, c->host_words[7], c->host_words[10], c->host_words[5]);
-    *done = true;
+    out->done = true;
     return SA_OK;
 }
