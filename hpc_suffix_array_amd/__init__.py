@@ -5,7 +5,7 @@ construction behind the C ABI of a-rtemis99/hpc_suffix_array
 from ._native import SAError, build_library, device_count, lib  # noqa: F401
 from .builder import (Collection, DeviceBuilder, FMIndex, LCEIndex, SuffixArray, build_suffix_array, bwt,  # noqa: F401
                       check_suffix_array, compare_substrings,
-                      count_patterns, doc_of_positions, document_array, document_frequency, find_patterns,
+                      count_patterns, doc_of_positions, document_array, document_frequency, edit_search, find_patterns,
                       hamming_search, inverse_bwt,
                       inverse_suffix_array, lcp_array, lcp_range_min, lf_mapping, list_documents,
                       locate_batch,
@@ -17,5 +17,5 @@ __all__ = ["SAError", "DeviceBuilder", "SuffixArray", "build_suffix_array", "che
            "match_patterns", "matching_statistics", "maximal_exact_matches", "longest_previous_factor", "lz77_factorize", "maximal_repeats", "bwt", "inverse_suffix_array",
            "lf_mapping", "inverse_bwt", "FMIndex", "document_array", "doc_of_positions", "document_frequency",
            "list_documents", "Collection", "longest_common_extension", "lcp_range_min", "compare_substrings",
-           "LCEIndex", "hamming_search", "build_library", "device_count",
+           "LCEIndex", "hamming_search", "edit_search", "build_library", "device_count",
            "lib"]

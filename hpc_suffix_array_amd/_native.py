@@ -123,6 +123,13 @@ HAMMING_LANE = 1
 HAMMING_WAVE = 2
 HAMMING_MODES = {"auto": 0, "lane": HAMMING_LANE, "wave": HAMMING_WAVE}
 HAMMING_LANE_BYTES = 8192
+# sa_edit (include/sa_hip.h SA_EDIT_*): the largest budget k (the band of
+# 2k + 1 diagonals fits a 64-bit word), the info words ([0] total ends, [1]
+# candidates, [2] pieces) and the positive status of a call stopped by
+# max_candidates
+EDIT_MAX_K = 31
+EDIT_INFO = 3
+EDIT_TOO_MANY = 1
 
 # every symbol include/*.h declares
 DROPIN_SYMBOLS = ["create_suffix_array", "destroy_suffix_array", "build_suffix_array",
@@ -147,6 +154,7 @@ EXT_SYMBOLS = ["sa_context_create", "sa_context_destroy", "sa_context_set_debug"
                "sa_lce_index_bytes", "sa_lce_build_device", "sa_lcp_min_device", "sa_lce_device",
                "sa_substr_compare_device", "sa_lcp_min", "sa_lce", "sa_substr_compare",
                "sa_hamming_device", "sa_hamming",
+               "sa_edit_device", "sa_edit",
                "sa_dist_begin", "sa_dist_cuts", "sa_dist_plan_cuts", "sa_dist_reserve", "sa_dist_release", "sa_dist_round1", "sa_dist_req_count", "sa_dist_req_fill",
                "sa_dist_answer", "sa_dist_refine",
                "sa_last_error", "sa_host_syncs", "sa_device_count", "sa_version", "sa_struct_size"]
@@ -377,6 +385,12 @@ def lib() -> ctypes.CDLL:
     L.sa_hamming.argtypes = [vp, u64, vp, i32, vp, vp, u64, u64, u64, ctypes.c_uint32, vp, vp, vp, u64,
                              ctypes.POINTER(u64)]
     L.sa_hamming.restype = i32
+    L.sa_edit_device.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, u64, u64, ctypes.c_uint32, vp, vp, vp, vp, u64,
+                                 ctypes.POINTER(u64), vp]
+    L.sa_edit_device.restype = i32
+    L.sa_edit.argtypes = [vp, u64, vp, i32, vp, vp, u64, u64, u64, ctypes.c_uint32, vp, vp, vp, vp, u64,
+                          ctypes.POINTER(u64)]
+    L.sa_edit.restype = i32
     L.sa_lpf_device.argtypes = [vp, vp, u64, vp, vp, vp, vp, vp]
     L.sa_lpf_device.restype = i32
     L.sa_lz77_device.argtypes = [vp, u64, vp, vp, vp, vp, vp, u64, ctypes.POINTER(u64), vp]

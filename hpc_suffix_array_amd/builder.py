@@ -484,6 +484,82 @@ def hamming_search(text, sa, patterns, k: int, max_candidates: int = 0, mode: st
                          max_candidates, mode, return_info)
 
 
+def _edit_k(k, max_candidates) -> None:
+    if not 0 <= int(k) <= N.EDIT_MAX_K:
+        raise ValueError(f"k = {k}: 0 .. {N.EDIT_MAX_K}")
+    if max_candidates < 0:
+        raise ValueError("max_candidates: 0 (none) or a positive bound")
+
+
+def _edit_host(t_ptr, n: int, sa_ptr, width: int, patterns, k: int, max_candidates: int, return_starts: bool,
+               return_info: bool):
+    """sa_edit over host pointers: a sizing call, then the call that fills the
+    arrays; (offsets int64, ends int64, starts int64, distances uint8), with
+    the info dict on request.  Without ``return_starts`` the backward DP is
+    skipped and starts / distances are None."""
+    _edit_k(k, max_candidates)
+    buf, poff = _pack_patterns(patterns)
+    nq = int(poff.size) - 1
+    off = np.zeros(nq + 1, dtype=np.uint64)
+    info = (ctypes.c_uint64 * N.EDIT_INFO)()
+    L = N.lib()
+
+    def call(end, start, dist, cap):
+        rc = N.check(L.sa_edit(t_ptr if n else None, n, sa_ptr if n else None, width,
+                               buf.ctypes.data if buf.size else None, poff.ctypes.data, nq, int(k),
+                               int(max_candidates), 0, off.ctypes.data,
+                               None if end is None else end.ctypes.data,
+                               None if start is None else start.ctypes.data,
+                               None if dist is None else dist.ctypes.data, cap, info), "sa_edit")
+        if rc == N.EDIT_TOO_MANY:
+            raise N.SAError(f"sa_edit: {int(info[1])} candidates are more than max_candidates = "
+                            f"{max_candidates} (raise it, or lower k)")
+
+    call(None, None, None, 0)
+    total = int(info[0])
+    wide = np.int64 if width == 8 else np.uint32
+    end = np.empty(max(total, 1), dtype=wide)
+    start = np.empty(max(total, 1), dtype=wide) if return_starts else None
+    dist = np.empty(max(total, 1), dtype=np.uint8) if return_starts else None
+    if total:
+        call(end, start, dist, total)
+        if int(info[0]) != total:
+            raise N.SAError(f"sa_edit: {int(info[0])} ends after a sizing call that counted {total}")
+    out = (off.astype(np.int64), end[:total].astype(np.int64),
+           start[:total].astype(np.int64) if return_starts else None, dist[:total].copy() if return_starts else None)
+    if return_info:
+        return out + ({"total": total, "candidates": int(info[1]), "pieces": int(info[2])},)
+    return out
+
+
+def edit_search(text, sa, patterns, k: int, max_candidates: int = 0, return_starts: bool = True,
+                return_info: bool = False):
+    """Occurrences of each pattern with at most ``k`` substitutions, insertions
+    and deletions, searched on the GPU (sa_edit).
+
+    ``text``, ``sa`` and ``patterns`` are those of find_patterns; ``k`` (0 ..
+    EDIT_MAX_K = 31) is the budget of every pattern of the call.  Returns
+    ``(offsets, ends, starts, distances)``: pattern q matches with at most k
+    edits at the ends ``ends[offsets[q]:offsets[q + 1]]`` (int64, ascending,
+    each once): ``e`` is listed when some ``text[s:e]`` is within edit distance
+    k of the pattern.  ``distances`` (uint8) is the least such distance D(e)
+    and ``starts`` (int64) the largest s that reaches it, the shortest best
+    match.  A pattern of up to ``k`` bytes would match at every end: it is not
+    searched and its list is empty.  A pattern longer than the text is
+    searched.  ``return_starts=False`` skips the pass that computes starts and
+    distances and returns None for both.  The work is proportional to the
+    candidates, the exact occurrences of the k + 1 pieces of every pattern:
+    ``max_candidates`` (0: none) raises SAError, with the count in the message,
+    instead of enumerating more than that.  ``return_info=True`` appends a
+    dict: ``total``, ``candidates`` and ``pieces`` (nq (k + 1))."""
+    t, s = _text_and_sa(text, sa)
+    _edit_k(k, max_candidates)
+    packed = _pack_patterns(patterns)
+    N.require_device()
+    return _edit_host(t.ctypes.data, int(t.size), s.ctypes.data, 8 if s.dtype == np.int64 else 4, packed, k,
+                      max_candidates, return_starts, return_info)
+
+
 def _none_to_minus_one(a: np.ndarray) -> np.ndarray:
     """uint32 / int64 results as int64, "none" (all ones at either width) as -1."""
     out = a.astype(np.int64)
@@ -1154,6 +1230,24 @@ class SuffixArray:
             and pattern_or_patterns.ndim == 1)
         out = _hamming_host(c.str, self.n, ctypes.cast(c.sa, ctypes.c_void_p).value, 4,
                             [pattern_or_patterns] if one else pattern_or_patterns, k, max_candidates, mode, return_info)
+        return out[1:] if one else out
+
+    def edit(self, pattern_or_patterns, k: int, max_candidates: int = 0, return_starts: bool = True,
+             return_info: bool = False):
+        """Occurrences with at most ``k`` substitutions, insertions and
+        deletions, as edit_search gives them (sa_edit at width 4 over the
+        object's own str / sa; build() first).  One pattern (bytes, str,
+        bytearray, memoryview or a uint8 array) returns ``(ends, starts,
+        distances)``; a sequence of patterns or a ``(buffer, offsets)`` pair
+        returns ``(offsets, ends, starts, distances)``."""
+        N.require_device()
+        c = self.p.contents
+        one = isinstance(pattern_or_patterns, (bytes, bytearray, memoryview, str)) or (
+            isinstance(pattern_or_patterns, np.ndarray) and pattern_or_patterns.dtype == np.uint8
+            and pattern_or_patterns.ndim == 1)
+        out = _edit_host(c.str, self.n, ctypes.cast(c.sa, ctypes.c_void_p).value, 4,
+                         [pattern_or_patterns] if one else pattern_or_patterns, k, max_candidates, return_starts,
+                         return_info)
         return out[1:] if one else out
 
     def lpf(self) -> tuple:
@@ -1929,6 +2023,30 @@ class DeviceBuilder:
                                               int(out_cap), info, s), "sa_hamming_device")
         if rc == N.HAMMING_TOO_MANY:
             raise N.SAError(f"sa_hamming_device: {int(info[1])} candidates are more than max_candidates = "
+                            f"{max_candidates}")
+        return int(info[0]), int(info[1]), int(info[2])
+
+    def edit(self, d_text, n: int, d_sa, d_pat, pat_bytes: int, d_pat_off, nq: int, k: int, d_off, d_end, d_start,
+             d_dist, out_cap: int, max_candidates: int = 0, stream=None) -> tuple:
+        """Occurrences with at most ``k`` edits of the nq patterns at d_pat
+        (pat_bytes bytes, nq + 1 uint64 offsets at d_pat_off), everything in
+        HBM (sa_edit_device): d_off nq + 1 uint64, d_end out_cap uint32 at any
+        4-byte alignment, d_start likewise or None, d_dist out_cap bytes or
+        None.  Returns ``(total, candidates, pieces)``.  Ends, starts and
+        distances are written only when the total fits out_cap and d_end is
+        not None: call once with ``d_end=None, d_start=None, d_dist=None`` to
+        size the outputs (d_off is filled), allocate, and call again.  Raises
+        SAError when the candidates exceed ``max_candidates``.  Waits for
+        ``stream``."""
+        _edit_k(k, max_candidates)
+        s = _stream(stream)
+        o = self._opt
+        info = (ctypes.c_uint64 * N.EDIT_INFO)()
+        rc = N.check(self.L.sa_edit_device(self.ctx, o(d_text), n, o(d_sa), o(d_pat), pat_bytes, o(d_pat_off), nq,
+                                           int(k), int(max_candidates), 0, o(d_off), o(d_end), o(d_start), o(d_dist),
+                                           int(out_cap), info, s), "sa_edit_device")
+        if rc == N.EDIT_TOO_MANY:
+            raise N.SAError(f"sa_edit_device: {int(info[1])} candidates are more than max_candidates = "
                             f"{max_candidates}")
         return int(info[0]), int(info[1]), int(info[2])
 

@@ -1658,6 +1658,11 @@ static int scan_i64(int64_t* d_v, uint64_t m, hipStream_t s) {
 // sa_query.h's tiles, the survivors sorted by its sort_lists
 #include "sa_hamming.h"
 
+// k-difference pattern search: sa_hamming.h's pieces as seeds, a banded
+// bit-vector DP per candidate over sa_query.h's tiles, the ends sorted by its
+// sort_lists and made unique, distances and starts by the DP run backwards
+#include "sa_edit.h"
+
 extern "C" {
 
 int sa_running_max_i64_device(int64_t* d_v, uint64_t m, void* stream) {

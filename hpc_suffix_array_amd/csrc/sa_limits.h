@@ -46,7 +46,7 @@ constexpr int kPlaceErrWord = 12;              // words[]: place_by_permutation'
 
 // The regions are the rows of this table alone, one per HwId in its order: a row left out has length 0 and fails below.
 enum HwId { kHwWords, kHwTotals, kHwUTotals, kHwGsInit, kHwLcpBest, kHwLcpCounts, kHwAlpha, kHwCode, kHwDistCounts, kHwTail,
-            kHwLocate, kHwMem, kHwLz, kHwRepeats, kHwIbwt, kHwFmTotals, kHwFmLocate, kHwDocs, kHwHamming, kHwCount };
+            kHwLocate, kHwMem, kHwLz, kHwRepeats, kHwIbwt, kHwFmTotals, kHwFmLocate, kHwDocs, kHwHamming, kHwEdit, kHwCount };
 constexpr HostRegion kHostRegions[kHwCount] = {
     {0, 16, false},        // kHwWords: the mirror of words[]
     {16, 3, false},        // kHwTotals: the segment totals of a round
@@ -67,6 +67,7 @@ constexpr HostRegion kHostRegions[kHwCount] = {
     {3460, 10, true},      // kHwFmLocate: index?, s, n, class | total
     {3520, 4, true},       // kHwDocs: total, long queries
     {3528, 4, true},       // kHwHamming: candidates | total
+    {3536, 6, true},       // kHwEdit: candidates | ends before the unique | total
 };
 constexpr HostRegion hw(HwId id) { return kHostRegions[id]; }
 

@@ -837,6 +837,85 @@ int sa_hamming(const uint8_t* text, uint64_t n, const void* sa, int sa_width, co
                uint64_t* off_out /* nq + 1 */, void* pos_out /* width sa_width */, uint8_t* dist_out, uint64_t out_cap,
                uint64_t info[SA_HAMMING_INFO]);
 
+/* ---- k-difference pattern search (edit distance) ---------------------------
+ * (csrc/sa_edit.h).  Text T of n bytes with its suffix array, a batch of nq
+ * patterns as sa_find takes them and one budget k for the call, 0 <= k <=
+ * SA_EDIT_MAX_K = 31 (the band of 2k + 1 <= 63 diagonals fits one 64-bit
+ * word).  Substitutions, insertions and deletions cost one each.
+ * For an end e in [0, n] let D(e) = min over s <= e of ed(P, T[s, e)), ed the
+ * unit-cost Levenshtein distance.  An occurrence of pattern P of m bytes is an
+ * end e with D(e) <= k; its distance is D(e) and its start the largest s with
+ * ed(P, T[s, e)) = D(e): the shortest best match.  A pattern with m <= k
+ * matches at every end: it is not searched and its list is empty, but its
+ * pieces are counted in info[2].  A pattern with m > n is searched (T = abc,
+ * P = abcd, k = 1: the end 3 at distance 1).  Bytes as sa_find has them.
+ * The output is CSR over the queries: off (nq + 1 uint64, off[0] = 0, the
+ * total is off[nq]), end (uint32, ascending inside each query, every end
+ * exactly once), start (uint32) and dist (uint8) of the same slot; start and
+ * dist may each be NULL, and neither may be given without end.
+ * info: SA_EDIT_INFO uint64 on the host: [0] the total (0 with
+ * SA_EDIT_TOO_MANY), [1] the candidates, [2] the pieces, nq (k + 1).
+ * max_candidates (0 = none): when the seed occurrences exceed it nothing is
+ * enumerated and the call returns SA_EDIT_TOO_MANY (a positive status, as
+ * SA_HAMMING_TOO_MANY) with the info words filled and off all zero.
+ * flags: none yet, must be 0.
+ * How it works: the pieces are sa_hamming's, b_j = floor(j m / (k + 1)); an
+ * alignment with at most k edits leaves one piece untouched, so it passes
+ * through an exact occurrence h of piece j, on the diagonal c = h - b_j
+ * (signed), and lies within the diagonals c - k .. c + k.  A lane runs the DP
+ * over that band for its candidate as a bit-vector kept in registers (a row
+ * step is one addition and a dozen logic operations; the row's equality word
+ * comes from 8-byte compares of the text against P[i]), stops when the whole
+ * row is above k, and leaves a 64-bit mask of the ends it found.  The ends are
+ * written in candidate order, sorted per query by sa_locate_device's sort
+ * (whose limit is inherited: more than 2^32 - 1 ends before the duplicates are
+ * removed are SA_E_INVALID), and the first of each run is kept.  Distances and
+ * starts come from the DP anchored at the end and run backwards over the
+ * diagonals -k .. k, once per end; it is skipped when neither is asked for.
+ * Temporaries are about 12.2 bytes per candidate on top of sa_locate_device's
+ * own, 8 bytes and a sort per end found and 24 bytes per piece.  DESIGN.md
+ * section 23. */
+#define SA_EDIT_MAX_K 31
+#define SA_EDIT_INFO 3
+#define SA_EDIT_TOO_MANY 1
+
+/* The buffers are sa_hamming_device's, with d_end / d_start (out_cap uint32
+ * each, any 4-byte alignment) and d_dist (out_cap bytes) in place of d_pos /
+ * d_dist.  When d_end is NULL, or when the total exceeds out_cap, d_off and
+ * info are filled, nothing in d_end / d_start / d_dist is touched and the call
+ * returns SA_OK: the sizing call, after which the caller allocates and calls
+ * again.  The sizing call does all the work but the backward DP.  Exactly
+ * [0, total) of the outputs given and d_off[0, nq] are written.
+ * Synchronises `stream`.  Host waits per call: one for the candidate count,
+ * sa_locate_device's own over the pieces, one for the ends found,
+ * sa_locate_device's own over them, one for the total and one at the end.
+ * nq == 0: SA_OK, off[0] = 0, no kernel.  n == 0: SA_OK, off all zero, no
+ * kernel.
+ * Checked before any HIP call (SA_E_INVALID, each with its own message, and
+ * nothing is written): a NULL ctx, info or d_off; a NULL d_text or d_sa with
+ * n > 0; a NULL d_pat with pat_bytes > 0; a NULL d_pat_off with nq > 0; n, nq
+ * or nq (k + 1) above 2^32 - 1; k above SA_EDIT_MAX_K; flags other than 0;
+ * d_start or d_dist without d_end; an output that is one of the inputs or
+ * another output.
+ * Precondition: d_sa is a valid suffix array of the text.  Without it
+ * occurrences may be missing, but no load leaves d_text[0, n), d_sa[0, n),
+ * d_pat[0, pat_bytes), the offsets or the temporaries: a hit >= n reads as no
+ * candidate and every text window is clipped to [0, n). */
+int sa_edit_device(sa_context* ctx, const uint8_t* d_text, uint64_t n, const uint32_t* d_sa, const uint8_t* d_pat,
+                   uint64_t pat_bytes, const uint64_t* d_pat_off /* nq + 1 */, uint64_t nq, uint64_t k,
+                   uint64_t max_candidates, uint32_t flags, uint64_t* d_off /* nq + 1 */, uint32_t* d_end,
+                   uint32_t* d_start, uint8_t* d_dist, uint64_t out_cap, uint64_t info[SA_EDIT_INFO], void* stream);
+/* Host in, host out as sa_hamming: sa, end_out and start_out have width
+ * sa_width (4 or 8), dist_out is uint8, pat_off must not decrease.  The total
+ * is found first and the device outputs are allocated then, so a caller may
+ * pass out_cap = 0 and NULL outputs to learn the total (info[0]) and off_out,
+ * and call again.  nq == 0 and n == 0 need no device.  Arguments are checked
+ * as the device form checks them. */
+int sa_edit(const uint8_t* text, uint64_t n, const void* sa, int sa_width, const uint8_t* pat,
+            const uint64_t* pat_off /* nq + 1 */, uint64_t nq, uint64_t k, uint64_t max_candidates, uint32_t flags,
+            uint64_t* off_out /* nq + 1 */, void* end_out /* width sa_width */, void* start_out /* width sa_width */,
+            uint8_t* dist_out, uint64_t out_cap, uint64_t info[SA_EDIT_INFO]);
+
 /* ---- maximal exact matches of a query against the text -------------------
  * (csrc/sa_mem.h).  Text T of n bytes with its suffix array, query Q of m
  * bytes, min_len = L >= 1.  A MEM is a triple (i, p, l) with all of:
